@@ -2,10 +2,18 @@
 """bench.py -- grid-points/s through the full TEM pipeline on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ne120x72x30] [--shard time|ncol]
+                  [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the whole hot path (theta, 7 projections, 4 native reconstructions,
 eddy products, zonal apply, fused epilogue -> the ten GM16 Table-A1 outputs) over synthetic
 fields already resident in HBM.  Plan build (basis + Gram + Cholesky) is timed separately.
+
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the line.  Everything
+else -- per-kernel roofline figures, the other BASELINE.json shapes (--also), the CPU baseline and
+the parity check against the oracle, and at N > 1 the legs beside the metric -- runs only with
+--full.  --dump-outputs DIR writes the ten results of the last timed step as DIR/<name>.npy
+(float64; a fixed, seeded sample of each when they exceed 64 MB in all); the synthetic inputs are
+seeded, so two runs with the same arguments compute from identical inputs.
 
 N = 1   : the workload BASELINE.json's target is quoted on, ne120 (777602 columns) x 72 lev x 30
           snapshots, fp64, on one GPU.
@@ -107,6 +115,24 @@ def cpu_baseline_config1_literal():
                       "(Y Y0inv) A as the reference associates them; best of 3"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, names, res):
+    """res: tensor [R][...] -> dirname/<name>.npy, float64.  When the R arrays exceed DUMP_LIMIT_BYTES
+    in all, each is replaced by a fixed sample of its flattened elements (seed 0, ascending positions),
+    so that two runs of the same shape dump the same positions."""
+    os.makedirs(dirname, exist_ok=True)
+    a = res.detach().double().cpu().numpy()
+    per = DUMP_LIMIT_BYTES // (len(names) * a.itemsize)
+    for i, n in enumerate(names):
+        x = a[i]
+        if x.size > per:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, per, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(dirname, n + ".npy"), np.ascontiguousarray(x))
+
+
 def self_launch(argv, ngpus):
     """`python bench.py --gpus N` without a launcher: become the parent of torch.distributed.run.
     Nothing here has touched the GPU (no HIP call, no torch.cuda query)."""
@@ -130,7 +156,7 @@ def main():
     ap.add_argument("--time-workload", default="ne30x72x730",
                     help="N > 1: the time-sharded job reported under other_workloads (BASELINE configs[2])")
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity check")
     ap.add_argument("--cpu-sample-nt", type=int, default=2)
     ap.add_argument("--no-symmetry", action="store_true",
                     help="force the generic sweeps (neither latitude classes nor mirror pairing)")
@@ -141,9 +167,9 @@ def main():
     ap.add_argument("--no-classes", action="store_true",
                     help="do not use the latitude-class sweeps (mirror-paired sweeps on a symmetric grid)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N > 1: skip the legs reported beside the metric (time-sharded configs[2], weak scaling)")
+                    help="N > 1 with --full: skip the legs reported beside the metric (time-sharded configs[2], weak scaling)")
     ap.add_argument("--also", default="ne30x72x1,ne30x72x91,ne30x72x92,ne240x128x1:f32,ne120x72x30:f32,ne120x72x30:f64:generic,ne120x72x30:f64:lat32,ne120x72x30:f64:shard1of8,ne120x72x4",
-                    help="comma list of the other BASELINE.json shapes, timed after the main one at N=1 "
+                    help="comma list of the other BASELINE.json shapes, timed after the main one at N=1 with --full "
                          "(shape[:f32|f64][:generic|:shardRofW]; ne30x72x91 is one rank's block of the 730-snapshot config cut evenly, "
                          "ne30x72x92 the block TimeShardedTEM cuts with multiple=aligned_snapshots (rows of whole 128-byte lines), "
                          "ne120x72x4 a time-sharded rank's block of configs[3] -- the no-collective alternative; "
@@ -155,7 +181,14 @@ def main():
                          "(rounds 1-3); default: latitudes as the construction leaves them, equal within a class to round-off")
     ap.add_argument("--stall-timeout", type=float, default=900.0,
                     help="N > 1: seconds the whole run may take before the watchdog reports a stalled collective")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ten results of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel roofline figures, the "
+                         "--also shapes, the CPU baseline with the parity check (N = 1), the legs beside the metric (N > 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.two_pass:
         os.environ["TEMX_TWO_PASS"] = "1"
     if args.class_sums:
@@ -183,7 +216,7 @@ def main():
         else:
             dist.init_process_group(backend=backend)
 
-    from pytemdiags_amd import engine, sharding, synth
+    from pytemdiags_amd import _lib, engine, sharding, synth
 
     ne, nlev, nt = parse_workload(args.workload)
     lat, lon = synth.cubed_sphere_gll(ne, mirror=args.exact_mirror)
@@ -253,12 +286,13 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    plan.kernel_timing(True)
+    if args.full:      # per-kernel HIP events behind the roofline entries; without them those entries are left out
+        plan.kernel_timing(True)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # the library launches on torch's current stream
     t0 = time.perf_counter()
     ev[0].record()
     for i in range(args.steps):
-        step()
+        last = step()
         ev[i + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -272,6 +306,13 @@ def main():
     proj_ms, nproj = plan.kernel_timing_read(0)
     eddy_ms, neddy = plan.kernel_timing_read(1)
     plan.kernel_timing(False)
+    if args.dump_outputs:
+        res_last = last[0]
+        if world > 1 and not (use_ncol and not runner.sliced):     # time-sharded results: the whole time axis on every rank
+            res_last = sharding.gather_time(res_last)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, _lib.RESULT_NAMES, res_last)
+        del res_last
 
     one_pass_main = plan.one_pass
     ms_per_step = elapsed / args.steps * 1e3
@@ -385,7 +426,7 @@ def main():
                                    "frac": gbs / PEAK_HBM_GBS, "avg_launch_ms": proj_ms,
                                    "mfma_tflops": 4 * 2 * K_HARM * pts_rank / (proj_ms * 1e-3) / 1e12}
 
-    if rank == 0 and world == 1 and args.also:
+    if args.full and rank == 0 and world == 1 and args.also:
         # other BASELINE.json shapes, same pipeline, reported beside the headline (not the metric)
         rec["other_workloads"] = {}
         for wl in [w for w in args.also.split(",") if w]:
@@ -483,7 +524,7 @@ def main():
                 rec["other_workloads"][wl] = {"error": "%s: %s" % (type(e).__name__, e)}
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         del fields
         torch.cuda.empty_cache()
         if one_pass_main:    # the sample has few d-tiles: make it take the code path that was timed
@@ -529,7 +570,7 @@ def main():
             errors[name] = "%s: %s" % (type(e).__name__, e)
         torch.cuda.empty_cache()
 
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         del fields, out
         torch.cuda.empty_cache()
 

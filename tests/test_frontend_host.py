@@ -221,6 +221,9 @@ def test_bench_self_launches_one_rank_per_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HIP_VISIBLE_DEVICES"] = ""                 # also on a GPU box: the ranks must not find a device
     env["CUDA_VISIBLE_DEVICES"] = ""
+    # the launcher stops the other ranks as soon as it sees one fail (polling every 0.1 s by default): poll every
+    # 10 s so that the slower rank, still importing torch, gets to its message too
+    env["PET_MONITOR_INTERVAL"] = "10"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
                         "--no-cpu-baseline", "--also", ""], capture_output=True, text=True, timeout=300, env=env)
     out = p.stdout + p.stderr

@@ -135,7 +135,7 @@ def test_bench_line_at_two_ranks_and_failure_exit_code():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["TEMX_BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--workload", "ne30x72x8", "--time-workload", "ne30x72x9", "--no-cpu-baseline"]
+           "--workload", "ne30x72x8", "--time-workload", "ne30x72x9", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

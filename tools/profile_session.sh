@@ -10,12 +10,12 @@ REPO=$PWD
 O=$REPO/gpurun_out/session_$R
 rm -rf "$O"
 mkdir -p "$O"
-python bench.py 2> "$O/bench.err" | tail -n 1 > "$O/bench.json"
+python bench.py --full 2> "$O/bench.err" | tail -n 1 > "$O/bench.json"
 echo "bench default done"
-python bench.py --no-cpu-baseline --class-sums --also= 2>> "$O/bench.err" | tail -n 1 > "$O/bench_classsums.json"
-python bench.py --no-cpu-baseline --two-pass --also= 2>> "$O/bench.err" | tail -n 1 > "$O/bench_twopass.json"
-python bench.py --no-cpu-baseline --no-classes --also= 2>> "$O/bench.err" | tail -n 1 > "$O/bench_paired.json"
-python bench.py --no-cpu-baseline --exact-mirror --also= 2>> "$O/bench.err" | tail -n 1 > "$O/bench_exact_mirror.json"
+python bench.py --full --no-cpu-baseline --class-sums --also= 2>> "$O/bench.err" | tail -n 1 > "$O/bench_classsums.json"
+python bench.py --full --no-cpu-baseline --two-pass --also= 2>> "$O/bench.err" | tail -n 1 > "$O/bench_twopass.json"
+python bench.py --full --no-cpu-baseline --no-classes --also= 2>> "$O/bench.err" | tail -n 1 > "$O/bench_paired.json"
+python bench.py --full --no-cpu-baseline --exact-mirror --also= 2>> "$O/bench.err" | tail -n 1 > "$O/bench_exact_mirror.json"
 echo "bench variants done"
 python tools/tracers_bench.py 120x72x30 f64 2 > "$O/tracers.log" 2>&1
 python tools/tracers_bench.py 120x72x30 f32 2 >> "$O/tracers.log" 2>&1
