@@ -72,15 +72,45 @@ enum {
                                       (env: TEMX_TRACER_ONE_PASS=1) */
   TEMX_OPT_SINGLE_SWEEP_MIN_GROUPS = 6, /* smallest number of class-groups for which the automatic choice takes the
                                       single sweep (default 640) */
-  TEMX_OPT_OS_CONTRACT = 7         /* single sweep, the contraction after it: 0 on the matrix cores (default), 1 the
+  TEMX_OPT_OS_CONTRACT = 7,        /* single sweep, the contraction after it: 0 on the matrix cores (default), 1 the
                                       round-3 form with the matrices staged in LDS (A/B; env: TEMX_OS_CONTRACT=lds) */
+  TEMX_OPT_MISSING = 8,            /* missing values: 0 = raise (default: a non-finite input is reported by
+                                      temx_status), 1 = mask (see "Missing-value mode" below).  Takes effect for the
+                                      TEM pipeline at the next temx_plan_set_tem, for temx_zonal_mean at once.
+                                      TEMX_EUNSUPPORTED for L > 63, weights-mode plans and plans finalised through the
+                                      pseudo-inverse */
+  TEMX_OPT_MIN_COVERAGE = 9,       /* missing-value mode: outputs whose coverage is below value / 1000 are NaN
+                                      (0..1000, default 500; 0 disables the coverage mask) */
+  TEMX_OPT_MISSING_WEIGHT = 10     /* missing-value mode: tau = 10^-value, the weight of a missing point as an
+                                      observation of 0 (4..14, default 10) */
 };
+/* Missing-value mode (TEMX_OPT_MISSING = 1).
+ *   Missing point: a value that is not finite (NaN, +-Inf).  TEM pipeline: one common mask per (column, level, time),
+ *     valid only where u, v, T and omega are all finite; the single-field operator: the field's own finiteness.
+ *     Sentinel fill values (1e20 ...) are data.
+ *   Masked fit: per (level, time) column d, f = sum_{l<=L} c_l Y_l^0 minimises
+ *       sum_{i valid} (a_i - f(lat_i))^2 + tau sum_{i missing} f(lat_i)^2
+ *     (every missing point an observation of 0 with weight tau): positive definite with a condition number of at
+ *     most about 1/tau, even when a whole latitude band is empty; exactly the default fit when nothing is missing.
+ *     The native mean xbar = f(lat_i), the eddies x' = x - xbar (NaN at missing points), the products u'v', u'omega',
+ *     v'theta' fitted the same way under the same mask, theta = T (p0/p)^kappa.
+ *   Coverage(lat, d): the DEFAULT operator applied to the validity indicator (1 valid, 0 missing) -- the spectral
+ *     zonal-mean valid fraction -- at the output latitudes (TEMX_MAT_COVERAGE) or at each column's own latitude.
+ *     Outputs are NaN where coverage < TEMX_OPT_MIN_COVERAGE; this never removes a valid point from a fit.  The seven
+ *     zonal means are masked before the epilogue; derivatives, psi, the pressure integral and the ten results take
+ *     NaN by IEEE propagation (np.gradient / cumulative trapezoid semantics).  Native outputs are NaN where the
+ *     point is missing or its coverage is below the threshold.  A column whose system does not factor is NaN in
+ *     every output.
+ *   Entry points: temx_zonal_mean (native 0 and 1), temx_tem_run, temx_tem_eddy and temx_tem_eddy_rows run masked;
+ *     temx_status reports 0 (non-finite input is data).  The staged, sharded and single-sweep entry points and every
+ *     tracer entry point return TEMX_EUNSUPPORTED in this mode. */
 enum {
   TEMX_FORM_AUTO = -1,
   TEMX_FORM_TWO_PASS = 0,          /* fields read twice (project sweep, eddy sweep) */
   TEMX_FORM_CLASS_SUMS = 1,        /* one pass with per-class sums + flux kernel wherever possible, never the single sweep */
   TEMX_FORM_SINGLE_SWEEP = 2,      /* the single sweep wherever its instantiations exist */
-  TEMX_FORM_NO_SINGLE_SWEEP = 3    /* automatic choice between the two forms above by problem size, never the single sweep */
+  TEMX_FORM_NO_SINGLE_SWEEP = 3,   /* automatic choice between the two forms above by problem size, never the single sweep */
+  TEMX_FORM_MASKED = 4             /* reported while missing-value mode is in effect: masked two-pass sweeps (any grid) */
 };
 
 /* which matrix temx_get_matrix copies */
@@ -94,8 +124,9 @@ enum {
                                   on (see temx_plan_finalize); the identity if the plan keeps the Y0 basis */
   TEMX_MAT_GX = 6,    /* [K][2L+1] Y0^T Y0ext over this rank's rows, Y0ext = Y_l^0 up to degree 2L (single sweep;
                                   after temx_plan_set_tem on a plan with temx_plan_single_sweep() == 1) */
-  TEMX_MAT_GSUB = 7   /* [KR][KR] Gram matrix of the first KR = min(16, K) harmonics over this rank's share of the
+  TEMX_MAT_GSUB = 7,  /* [KR][KR] Gram matrix of the first KR = min(16, K) harmonics over this rank's share of the
                                   reference subsample (single sweep) */
+  TEMX_MAT_COVERAGE = 8 /* [M][D] zonal-grid coverage of the latest masked run on this plan (TEMX_ESTATE before one) */
 };
 
 /* order of the ten GM16 Table-A1 results in the results buffer (tem_diagnostics.py:1018-1022) */

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TEMX_LIB") or os.path.join(_HERE, "libtemx.so")   # TEMX_LIB: A/B builds
 
-ABI_VERSION = 401           # temx_version() of the library these bindings were written for (include/temx.h)
+ABI_VERSION = 402           # temx_version() of the library these bindings were written for (include/temx.h)
 F64, F32 = 0, 1
 DEFER_FINALIZE = 1
 NO_SYMMETRY = 2
@@ -19,9 +19,14 @@ NO_CLASSES = 4
 NO_QR = 8
 LAT_TOL_F32 = 16
 MAT_Y0, MAT_Y0P, MAT_GRAM, MAT_GINV, MAT_Y0INV, MAT_GRAM2, MAT_GX, MAT_GSUB = 0, 1, 2, 3, 4, 5, 6, 7
+MAT_COVERAGE = 8
 # temx_plan_configure options and the forms of the latitude-class sweeps (include/temx.h)
 OPT_FORM, OPT_OS_MAP, OPT_OP_MAP, OPT_OS_SUBSAMPLE, OPT_TRACER_ONE_PASS, OPT_SINGLE_SWEEP_MIN_GROUPS, OPT_OS_CONTRACT = 1, 2, 3, 4, 5, 6, 7
+# missing-value mode (include/temx.h): 0 raise / 1 mask, coverage threshold in per mille, tau = 10^-value
+OPT_MISSING, OPT_MIN_COVERAGE, OPT_MISSING_WEIGHT = 8, 9, 10
+MISSING_MODES = {"raise": 0, "mask": 1}
 FORM_AUTO, FORM_TWO_PASS, FORM_CLASS_SUMS, FORM_SINGLE_SWEEP, FORM_NO_SINGLE_SWEEP = -1, 0, 1, 2, 3
+FORM_MASKED = 4
 FORMS = {"auto": FORM_AUTO, "two-pass": FORM_TWO_PASS, "class-sums": FORM_CLASS_SUMS,
          "single-sweep": FORM_SINGLE_SWEEP, "no-single-sweep": FORM_NO_SINGLE_SWEEP}
 

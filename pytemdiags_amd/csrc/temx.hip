@@ -25,6 +25,7 @@
 #include "kernels_op2.hpp"
 #include "kernels_osc.hpp"
 #include "side_tables.hpp"
+#include "kernels_miss.hpp"
 
 using namespace temx;
 
@@ -185,6 +186,16 @@ struct temx_plan {
   DevBuf partial;
   // operator-API workspace (any D)
   DevBuf opB, opC;
+  // missing-value mode (kernels_miss.hpp; TEMX_OPT_MISSING, TEMX_OPT_MIN_COVERAGE, TEMX_OPT_MISSING_WEIGHT)
+  int opt_missing = 0, opt_min_cov = 500, opt_miss_w = 10;
+  bool miss_built = false;             // eblk and mtab describe the plan's current basis
+  bool miss_valid = false;             // mC / mCcov hold the coefficients of the latest masked temx_tem_run
+  int64_t miss_cov_D = -1;             // columns of the coverage of the latest masked run (-1: none yet)
+  int NE = 0, NQM = 0;                 // raw harmonics of the missing indicator (2L+1), Gauss nodes of H (2L+1)
+  DevBuf eblk;                         // raw rows to degree 2L as 4x4 blocks, 2 TB blocks per group
+  DevBuf mtab;                         // G2 [K][K], Zq [NQ][K], Yq [NQ][NE], Acov [K][K], c1 [K]
+  DevBuf mB, mC, mCcov, mcov, mZ;      // sums [4K + NE][D], coefficients [4][K4][D], coverage coefficients [K4][D],
+                                       // coverage [M][D], zonal scratch of the native operator [M][D]
   // timing hooks
   bool timing = false;
   std::vector<TimedLaunch> timed[2];
@@ -509,7 +520,7 @@ template <typename T, int MODE, int DPW, int KIND>
 static int launch_eddy_d(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
                          const Split& sp, const EddyOut& eo, hipStream_t st) {
   dim3 grid(sp.grid), block(512);
-  constexpr int NFR = KIND == 0 ? 4 : 3;
+  constexpr int NFR = KIND == 1 ? 3 : 4;
 #define TEMX_LE(TBv)                                                                                  \
   do {                                                                                                \
     auto kern = eddy_kernel<T, TBv, MODE, DPW, KIND>;                                                 \
@@ -1786,6 +1797,9 @@ static void set_tail(temx_plan* pl, int64_t t0, int64_t nts) {
 static inline bool tail_is_whole(const temx_plan* pl) { return pl->tt0 == 0 && pl->tnt == pl->nt; }
 
 static int tem_stage3_impl(temx_plan* pl, const double* B3, double* results, double* zonal, hipStream_t st);
+static int tem_epilogue(temx_plan* pl, double* results, double* zonal, hipStream_t st);
+static int miss_check(const temx_plan* pl);
+static int miss_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* out, int native, hipStream_t st);
 static int tracer_stage3_impl(temx_plan* pl, const double* Bq2, double* tres, double* tzon, hipStream_t st);
 
 // Time slices of a reduction (kernels.hpp, SliceMap): nsl slices, rows_total rows per slice
@@ -2047,9 +2061,104 @@ static int tracer_run_os(temx_plan* pl, int nq, const void* const* q, const void
   catch (const std::exception& e_) { return fail(TEMX_EINTERNAL, "unexpected C++ exception: %s", e_.what()); } \
   catch (...) { return fail(TEMX_EINTERNAL, "unexpected C++ exception"); }
 
+// ---- missing-value mode: launchers (kernels_miss.hpp) ---------------------------------------------------------
+static inline bool miss_mode(const temx_plan* pl) { return pl->opt_missing == 1; }
+static inline double miss_thr(const temx_plan* pl) { return pl->opt_min_cov / 1000.0; }
+static inline double miss_omt(const temx_plan* pl) { return 1.0 - std::pow(10.0, -(double)pl->opt_miss_w); }
+static int miss_refuse(const char* what) {
+  return fail(TEMX_EUNSUPPORTED, "%s is not available in missing-value mode (TEMX_OPT_MISSING = 1): the masked path "
+                                 "serves temx_zonal_mean, temx_tem_run and the eddy entry points only", what);
+}
+
+// out[NF K + NE][D]: select-projections of the NF fields, then the projection of their common missing indicator
+template <typename T, int NF>
+static int launch_miss_project_t(temx_plan* pl, const FieldPtrs<NF>& fp, int64_t D, const double* colscale, int sfield,
+                                 double* out, hipStream_t st) {
+  const Split sp = choose_split(D, pl->nchunk, pl->num_cu, 4);
+  const int64_t R = (int64_t)NF * pl->K + pl->NE;
+  if (int rc = pl->partial.ensure(std::max((size_t)sp.nsplit * R * D * 8, pl->partial.bytes))) return rc;
+#define TEMX_LM(TBv)                                                                                              \
+  hipLaunchKernelGGL((miss_project_kernel<T, NF, TBv, 2 * TBv>), dim3(sp.grid), dim3(256), 0, st, fp, pl->N, D, pl->K, \
+                     pl->NE, pl->yblk.d(), pl->stride, pl->eblk.d(), pl->nchunk, colscale, sfield, pl->partial.d(),  \
+                     sp.nsplit, sp.ndt)
+  switch (pl->TB) {
+    case 4: TEMX_LM(4); break;
+    case 8: TEMX_LM(8); break;
+    case 13: TEMX_LM(13); break;
+    default: TEMX_LM(16); break;
+  }
+#undef TEMX_LM
+  HIPCHK(hipGetLastError());
+  return launch_reduce(pl, pl->partial.d(), sp.nsplit, R * D, out, st);
+}
+template <int NF>
+static int launch_miss_project(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int64_t D, const double* colscale,
+                               int sfield, double* out, hipStream_t st) {
+  if (dtype == TEMX_F64) return launch_miss_project_t<double, NF>(pl, fp, D, colscale, sfield, out, st);
+  if (dtype == TEMX_F32) return launch_miss_project_t<float, NF>(pl, fp, D, colscale, sfield, out, st);
+  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+}
+
+template <int NR>
+static int launch_miss_system(temx_plan* pl, const double* Bf, const double* E, int64_t D, double* C, double* Ccov,
+                              double* zout, double* cov, hipStream_t st) {
+  const int K = pl->K, NQ = pl->NQM, NE = pl->NE;
+  const double* t = pl->mtab.d();
+  MissTables tb;
+  tb.G2 = t;
+  tb.Zq = tb.G2 + (size_t)K * K;
+  tb.Yq = tb.Zq + (size_t)NQ * K;
+  tb.Acov = tb.Yq + (size_t)NQ * NE;
+  tb.c1 = tb.Acov + (size_t)K * K;
+  tb.Qp = pl->Qp.d();
+  hipLaunchKernelGGL(miss_system_kernel<NR>, dim3((unsigned)D), dim3(256), 0, st, Bf, E, K, pl->K4, NE, NQ, pl->M, D, tb,
+                     miss_omt(pl), miss_thr(pl), C, Ccov, zout, cov);
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+// the masked eddy sweep: products under the common mask, projected on Q (generic sweep on every grid)
+static int launch_miss_eddy(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, hipStream_t st) {
+  EddyOut none{};
+  if (dtype == TEMX_F64) return launch_eddy_t<double, 0, 2>(pl, fp, pl->mC.d(), pl->partial.d(), pl->sp_eddy, none, st);
+  if (dtype == TEMX_F32) return launch_eddy_t<float, 0, 2>(pl, fp, pl->mC.d(), pl->partial.d(), pl->sp_eddy, none, st);
+  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+}
+
+static int launch_miss_eddy_native(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, int64_t row0, int64_t nrows,
+                                   const EddyOut& eo, hipStream_t st) {
+  const int64_t n = nrows * pl->D;
+  const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)pl->num_cu * 16));
+#define TEMX_LMN(T)                                                                                                   \
+  hipLaunchKernelGGL(miss_eddy_native_kernel<T>, grid, dim3(256), 0, st, fp, row0, nrows, pl->D, pl->K, pl->K4,        \
+                     pl->yblk.d(), pl->stride, pl->mC.d(), pl->mCcov.d(), pl->colscale.d(), miss_thr(pl), eo)
+  if (dtype == TEMX_F64) TEMX_LMN(double);
+  else if (dtype == TEMX_F32) TEMX_LMN(float);
+  else return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+#undef TEMX_LMN
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+static int launch_miss_native(temx_plan* pl, const void* A, int dtype, int64_t D, const double* C, const double* Ccov,
+                              double* out, hipStream_t st) {
+  const int64_t n = pl->N * D;
+  const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)pl->num_cu * 16));
+  if (dtype == TEMX_F64)
+    hipLaunchKernelGGL(miss_native_kernel<double>, grid, dim3(256), 0, st, static_cast<const double*>(A), pl->N, D, pl->K,
+                       pl->yblk.d(), pl->stride, C, Ccov, miss_thr(pl), out);
+  else if (dtype == TEMX_F32)
+    hipLaunchKernelGGL(miss_native_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(A), pl->N, D, pl->K,
+                       pl->yblk.d(), pl->stride, C, Ccov, miss_thr(pl), out);
+  else
+    return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
 extern "C" {
 
-int temx_version(void) { return 401; }
+int temx_version(void) { return 402; }
 
 const char* temx_last_error(void) { return g_err.c_str(); }
 
@@ -2082,6 +2191,7 @@ void temx_plan_destroy(temx_plan* pl) {
                     &pl->side_gfirst[0][0], &pl->side_gfirst[0][1], &pl->side_gfirst[1][0], &pl->side_gfirst[1][1], &pl->rho,
                     &pl->rho0, &pl->gaunt, &pl->wq2, &pl->Axq, &pl->rho_t, &pl->Gx, &pl->Gsinv, &pl->Ax, &pl->Axs, &pl->oscblk, &pl->osAt, &pl->osAb, &pl->osAtq, &pl->osAbq, &pl->Bqp})
     b->release();
+  for (DevBuf* b : {&pl->eblk, &pl->mtab, &pl->mB, &pl->mC, &pl->mCcov, &pl->mcov, &pl->mZ}) b->release();
   for (auto& kv : pl->csplits_s) kv.second.release();
   for (auto& kv : pl->csplits) kv.second.release();
   for (int w = 0; w < 2; ++w)
@@ -2431,6 +2541,7 @@ int temx_plan_finalize(temx_plan* pl, const double* G_host) try {
   HIPCHK(hipMemcpy(pl->flag.p, &zero, sizeof(int), hipMemcpyHostToDevice));
   pl->finalized = true;
   pl->op_valid = pl->c4_valid = pl->xb_valid = pl->tq_valid = false;   // sums / coefficients of another basis
+  pl->miss_built = pl->miss_valid = false;
   // one process owns all the rows: second pass of the re-orthogonalisation with its own Gram matrix of Q
   if (want_q && !G_host) return temx_plan_refine(pl, nullptr);
   return TEMX_OK;
@@ -2458,6 +2569,7 @@ int temx_plan_refine(temx_plan* pl, const double* G2_host) try {
   std::vector<long double> Li;
   if (spd_factor(G2.data(), K, Li) != 0) return TEMX_OK;   // (cannot happen for Q^T Q ~ I; keep the identity)
   inverse_from_factor(Li, K, Gi.data());
+  pl->miss_built = pl->miss_valid = false;
   return set_ginv(pl, Gi.data());
 } TEMX_CATCH
 
@@ -2497,6 +2609,7 @@ int temx_plan_set_weights(temx_plan* pl, const double* w_host) try {
   pl->tem = false;                // splits / workspaces belong to the path: set_tem again
   pl->weighted = true;
   pl->finalized = true;
+  pl->miss_built = pl->miss_valid = false;
   return TEMX_OK;
 } TEMX_CATCH
 
@@ -2548,6 +2661,10 @@ int temx_get_matrix(temx_plan* pl, int which, double* dst, void* stream) try {
       HIPCHK(hipMemcpy(dst, h.data(), h.size() * 8, hipMemcpyHostToDevice));
       return TEMX_OK;
     }
+    case TEMX_MAT_COVERAGE:
+      if (pl->miss_cov_D < 0) return fail(TEMX_ESTATE, "no masked run on this plan yet (TEMX_OPT_MISSING = 1)");
+      HIPCHK(hipMemcpyAsync(dst, pl->mcov.p, (size_t)pl->M * pl->miss_cov_D * 8, hipMemcpyDeviceToDevice, st));
+      return TEMX_OK;
     default:
       return fail(TEMX_EINVAL, "unknown matrix id %d", which);
   }
@@ -2578,6 +2695,7 @@ int temx_plan_set_os_matrices(temx_plan* pl, const double* Gx_host, const double
 
 // ---- operator API --------------------------------------------------------------------------------
 int temx_project(temx_plan* pl, const void* A, int dtype, int64_t D, double* B, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_project");
   if (!pl || !A || !B) return fail(TEMX_EINVAL, "null argument");
   if (D < 1 || D >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "D must be in [1, 2^28)");
   HIPCHK(hipSetDevice(pl->device));
@@ -2598,6 +2716,7 @@ int temx_project(temx_plan* pl, const void* A, int dtype, int64_t D, double* B, 
 
 int temx_zonal_mean_from_sums(temx_plan* pl, const double* B, int64_t D, double* out, int native,
                               void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_zonal_mean_from_sums");
   if (!pl || !B || !out) return fail(TEMX_EINVAL, "null argument");
   if (!pl->finalized) return fail(TEMX_ESTATE, "plan not finalised");
   HIPCHK(hipSetDevice(pl->device));
@@ -2612,6 +2731,7 @@ int temx_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* 
                     void* stream) try {
   if (!pl || !A || !out) return fail(TEMX_EINVAL, "null argument");
   if (!pl->finalized) return fail(TEMX_ESTATE, "plan not finalised");
+  if (miss_mode(pl)) return miss_zonal_mean(pl, A, dtype, D, out, native, S_(stream));
   int rc = pl->opB.ensure((size_t)pl->K * std::max<int64_t>(D, 1) * 8);
   if (rc) return rc;
   if ((rc = temx_project(pl, A, dtype, D, pl->opB.d(), stream))) return rc;
@@ -2665,6 +2785,21 @@ int temx_plan_configure(temx_plan* pl, int option, int value) try {
       break;
     case TEMX_OPT_SINGLE_SWEEP_MIN_GROUPS: pl->opt_single_sweep_min_groups = value; break;
     case TEMX_OPT_OS_CONTRACT: pl->opt_os_contract = value; break;
+    case TEMX_OPT_MISSING:
+      if (value != 0 && value != 1) return fail(TEMX_EINVAL, "TEMX_OPT_MISSING: 0 (raise) or 1 (mask), got %d", value);
+      if (value == 1)
+        if (int rc = miss_check(pl)) return rc;
+      pl->opt_missing = value;
+      pl->miss_valid = false;
+      break;
+    case TEMX_OPT_MIN_COVERAGE:
+      if (value < 0 || value > 1000) return fail(TEMX_EINVAL, "TEMX_OPT_MIN_COVERAGE: per mille in 0..1000, got %d", value);
+      pl->opt_min_cov = value;
+      break;
+    case TEMX_OPT_MISSING_WEIGHT:
+      if (value < 4 || value > 14) return fail(TEMX_EINVAL, "TEMX_OPT_MISSING_WEIGHT: tau = 10^-value, value in 4..14, got %d", value);
+      pl->opt_miss_w = value;
+      break;
     default: return fail(TEMX_EINVAL, "unknown option %d", option);
   }
   pl->tem = false;                // the choice is made in temx_plan_set_tem: call it (again)
@@ -2674,13 +2809,18 @@ int temx_plan_configure(temx_plan* pl, int option, int value) try {
 int temx_plan_option(const temx_plan* pl, int option) try {
   if (!pl) return -1;
   switch (option) {
-    case TEMX_OPT_FORM: return pl->os_on ? TEMX_FORM_SINGLE_SWEEP : ((pl->cls && pl->onepass) || (pl->lcls && pl->lone) ? TEMX_FORM_CLASS_SUMS : TEMX_FORM_TWO_PASS);
+    case TEMX_OPT_FORM:
+      if (miss_mode(pl)) return TEMX_FORM_MASKED;
+      return pl->os_on ? TEMX_FORM_SINGLE_SWEEP : ((pl->cls && pl->onepass) || (pl->lcls && pl->lone) ? TEMX_FORM_CLASS_SUMS : TEMX_FORM_TWO_PASS);
     case TEMX_OPT_OS_MAP: return tile_map(pl->opt_os_map, "TEMX_OS_MAP") ? 1 : 0;
     case TEMX_OPT_OP_MAP: return tile_map(pl->opt_op_map, "TEMX_OP_MAP") ? 1 : 0;
     case TEMX_OPT_TRACER_ONE_PASS: return tracer_one_pass_wanted(pl) ? 1 : 0;
     case TEMX_OPT_OS_SUBSAMPLE: return pl->os_keep;
     case TEMX_OPT_SINGLE_SWEEP_MIN_GROUPS: return pl->opt_single_sweep_min_groups;
     case TEMX_OPT_OS_CONTRACT: return pl->osc_lds ? 1 : 0;
+    case TEMX_OPT_MISSING: return pl->opt_missing;
+    case TEMX_OPT_MIN_COVERAGE: return pl->opt_min_cov;
+    case TEMX_OPT_MISSING_WEIGHT: return pl->opt_miss_w;
     default: return -1;
   }
 } TEMX_CATCH
@@ -2899,6 +3039,7 @@ static int tem_ready(temx_plan* pl) {
 
 int temx_tem_stage1(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                     int dtype, double* B4, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_stage1");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !B4) return fail(TEMX_EINVAL, "null argument");
@@ -3015,6 +3156,7 @@ static int tem_stage2_large(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, co
 
 int temx_tem_stage2(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                     int dtype, const double* B4, double* B3, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_stage2");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !B4 || !B3) return fail(TEMX_EINVAL, "null argument");
@@ -3034,6 +3176,7 @@ int temx_tem_stage2(temx_plan* pl, const void* ua, const void* va, const void* t
 } TEMX_CATCH
 
 int temx_tem_stage2_from_sums(temx_plan* pl, const double* B4, double* B3, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_stage2_from_sums");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!B4 || !B3) return fail(TEMX_EINVAL, "null argument");
@@ -3062,6 +3205,7 @@ int temx_tem_stage2_from_sums(temx_plan* pl, const double* B4, double* B3, void*
 } TEMX_CATCH
 
 int temx_tem_stage3(temx_plan* pl, const double* B3, double* results, double* zonal, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_stage3");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!B3 || !results) return fail(TEMX_EINVAL, "null argument");
@@ -3076,10 +3220,17 @@ int temx_tem_stage3(temx_plan* pl, const double* B3, double* results, double* zo
 // zb[0..3] hold the zonal means of the four fields for the same snapshots)
 static int tem_stage3_impl(temx_plan* pl, const double* B3, double* results, double* zonal, hipStream_t st) {
   int rc;
-  const int64_t Dt = pl->tD, nts = pl->tnt;
+  const int64_t Dt = pl->tD;
   const int64_t MD = (int64_t)pl->M * Dt;
   // flux zonal means upvpb upwappb vptpb -> zb[4..6]
   if ((rc = launch_solve(pl, B3, 3, Dt, nullptr, pl->zb.d() + 4 * MD, st))) return rc;
+  return tem_epilogue(pl, results, zonal, st);
+}
+
+// int_vbdp, derivatives, psi and the ten diagnostics from the seven zonal means in zb[0..6]
+static int tem_epilogue(temx_plan* pl, double* results, double* zonal, hipStream_t st) {
+  const int64_t Dt = pl->tD, nts = pl->tnt;
+  const int64_t MD = (int64_t)pl->M * Dt;
   // int_vbdp -> zb[7]: by a wavefront scan; inside the epilogue only for short columns on small zonal grids
   // (measured: at nlev = 72 the O(nlev) loop per point costs what the extra launch saves, at 128 more)
   EpiTables tb{pl->p.d(), pl->pg.d(), pl->lg.d(), pl->coslat.d(), pl->fcor.d()};
@@ -3119,6 +3270,7 @@ static int slices_ok(const temx_plan* pl, int nslices) {
 
 int temx_tem_os_prepass(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap, int dtype,
                         double* As, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_os_prepass");
   int rc = os_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !As) return fail(TEMX_EINVAL, "null argument");
@@ -3129,6 +3281,7 @@ int temx_tem_os_prepass(temx_plan* pl, const void* ua, const void* va, const voi
 
 int temx_tem_os_sweep(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap, int dtype,
                       const double* As, int nslices, double* proj, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_os_sweep");
   int rc = os_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !As || !proj) return fail(TEMX_EINVAL, "null argument");
@@ -3140,6 +3293,7 @@ int temx_tem_os_sweep(temx_plan* pl, const void* ua, const void* va, const void*
 
 int temx_tem_os_tail(temx_plan* pl, const double* proj_slice, int64_t t0, int64_t nts, double* results, double* zonal,
                      void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_os_tail");
   int rc = os_ready(pl);
   if (rc) return rc;
   if (!proj_slice || !results) return fail(TEMX_EINVAL, "null argument");
@@ -3160,6 +3314,7 @@ static int tracers_args(const temx_plan* pl, int nq, const void* const* q_host, 
 
 int temx_tracers_os_prepass(temx_plan* pl, int nq, const void* const* q_host, const void* va, const void* wap, int dtype,
                             double* Asq, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracers_os_prepass");
   int rc = os_ready(pl);
   if (rc) return rc;
   if ((rc = tracers_args(pl, nq, q_host, va, wap, dtype))) return rc;
@@ -3170,6 +3325,7 @@ int temx_tracers_os_prepass(temx_plan* pl, int nq, const void* const* q_host, co
 
 int temx_tracers_os_sweep(temx_plan* pl, int nq, const void* const* q_host, const void* va, const void* wap, int dtype,
                           const double* Asq, int nslices, double* projq, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracers_os_sweep");
   int rc = os_ready(pl);
   if (rc) return rc;
   if ((rc = tracers_args(pl, nq, q_host, va, wap, dtype))) return rc;
@@ -3181,6 +3337,7 @@ int temx_tracers_os_sweep(temx_plan* pl, int nq, const void* const* q_host, cons
 
 int temx_tracers_os_tail(temx_plan* pl, int nq, const double* projq_slice, double* const* tres_host, double* const* tzon_host,
                          void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracers_os_tail");
   int rc = os_ready(pl);
   if (rc) return rc;
   if (nq != 1 && nq != 2) return fail(TEMX_EINVAL, "nq = %d: one or two tracers per sweep", nq);
@@ -3195,6 +3352,7 @@ int temx_tracers_os_tail(temx_plan* pl, int nq, const double* projq_slice, doubl
 // stages 2b + 3 on a time slice, from raw sums of any form of the sweeps: B4s [4][K][nlev][nts], B3s [3][K][nlev][nts]
 int temx_tem_tail_from_sums(temx_plan* pl, const double* B4s, const double* B3s, int64_t t0, int64_t nts, double* results,
                             double* zonal, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_tail_from_sums");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!B4s || !B3s || !results) return fail(TEMX_EINVAL, "null argument");
@@ -3219,10 +3377,162 @@ int temx_time_slices(temx_plan* pl, const double* B, int64_t rows, int nslices, 
   return launch_reduce(pl, B, 1, rows * pl->D, out, S_(stream), -1, nullptr, slice_map(pl, nslices, rows, 0));
 } TEMX_CATCH
 
+// ---- missing-value mode (kernels_miss.hpp): tables, the masked TEM run and the masked operator ------------------
+// configurations the masked path serves (checked at temx_plan_configure and again before every masked run)
+static int miss_check(const temx_plan* pl) {
+  if (pl->K > 64) return fail(TEMX_EUNSUPPORTED, "missing-value mode: L = %d, this version supports L <= 63", pl->L);
+  if (pl->weighted) return fail(TEMX_EUNSUPPORTED, "missing-value mode is not available on a weights-mode plan");
+  if (pl->finalized && pl->rank < pl->K)
+    return fail(TEMX_EUNSUPPORTED, "missing-value mode: the plan was finalised through the pseudo-inverse (rank %d < K = %d; "
+                                   "fewer distinct latitudes than harmonics)", pl->rank, pl->K);
+  return TEMX_OK;
+}
+
+// Built once per basis: the raw rows of the e projection and the tables of the per-d systems (kernels_miss.hpp)
+static int miss_setup(temx_plan* pl) {
+  if (!pl->finalized) return fail(TEMX_ESTATE, "plan not finalised");
+  if (int rc = miss_check(pl)) return rc;
+  if (pl->miss_built) return TEMX_OK;
+  const int K = pl->K, NE = 2 * pl->L + 1, NQ = 2 * pl->L + 1, TBE = 2 * pl->TB;
+  int rc;
+  pl->NE = NE;
+  pl->NQM = NQ;
+  const int64_t npad = pl->nchunk * 16;
+  if ((rc = pl->eblk.ensure((size_t)pl->nchunk * 4 * TBE * 16 * 8))) return rc;
+  hipLaunchKernelGGL(miss_basis_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, 0, pl->x.d(), pl->N, npad, NE,
+                     TBE, pl->eblk.d());
+  HIPCHK(hipGetLastError());
+  // Q^T Q over this plan's rows (Y0^T Y0 when the plan keeps the Y0 basis)
+  std::vector<double> G2((size_t)K * K), T((size_t)K * K, 0.0);
+  if (pl->qbasis) {
+    if ((rc = gram_of_q(pl))) return rc;
+    HIPCHK(hipMemcpy(G2.data(), pl->G2.p, G2.size() * 8, hipMemcpyDeviceToHost));
+    T = pl->h_T;
+  } else {
+    HIPCHK(hipMemcpy(G2.data(), pl->G.p, G2.size() * 8, hipMemcpyDeviceToHost));
+    for (int l = 0; l < K; ++l) T[(size_t)l * K + l] = 1.0;
+  }
+  const std::vector<double>& Gi = pl->h_Ginv;   // the default operator: coefficients = Gi Q^T a
+  // s = Y0^T 1 (raw), from the latitudes
+  std::vector<double> xs((size_t)pl->N);
+  HIPCHK(hipMemcpy(xs.data(), pl->x.p, xs.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<long double> s(K, 0.0L), y(std::max(K, NE));
+  for (int64_t i = 0; i < pl->N; ++i) {
+    ylm0_row(xs[i], K, y.data());
+    for (int l = 0; l < K; ++l) s[l] += y[l];
+  }
+  std::vector<double> tab;
+  tab.reserve((size_t)2 * K * K + (size_t)NQ * (K + NE) + K);
+  tab.insert(tab.end(), G2.begin(), G2.end());
+  std::vector<long double> xq, wq;
+  gauss_legendre(NQ, xq, wq);
+  const long double twopi = 6.283185307179586476925286766559005768L;
+  std::vector<double> Yq((size_t)NQ * NE);
+  for (int q = 0; q < NQ; ++q) {                    // Zq[q][j] = sum_l Y_l(x_q) T[l][j]
+    ylm0_row(xq[q], NE, y.data());
+    for (int j = 0; j < K; ++j) {
+      long double a = 0.0L;
+      for (int l = 0; l <= j; ++l) a += y[l] * T[(size_t)l * K + j];
+      tab.push_back((double)a);
+    }
+    for (int n = 0; n < NE; ++n) Yq[(size_t)q * NE + n] = (double)(twopi * wq[q] * y[n]);
+  }
+  tab.insert(tab.end(), Yq.begin(), Yq.end());
+  std::vector<long double> sQ(K, 0.0L);            // Q^T 1 = T^T s
+  for (int j = 0; j < K; ++j)
+    for (int l = 0; l <= j; ++l) sQ[j] += s[l] * T[(size_t)l * K + j];
+  for (int j = 0; j < K; ++j)                       // Acov = Gi T^T
+    for (int l = 0; l < K; ++l) {
+      long double a = 0.0L;
+      for (int k = 0; k < K; ++k) a += (long double)Gi[(size_t)j * K + k] * T[(size_t)l * K + k];
+      tab.push_back((double)a);
+    }
+  for (int j = 0; j < K; ++j) {                     // c1 = Gi Q^T 1
+    long double a = 0.0L;
+    for (int k = 0; k < K; ++k) a += (long double)Gi[(size_t)j * K + k] * sQ[k];
+    tab.push_back((double)a);
+  }
+  if ((rc = upload(pl->mtab, tab.data(), tab.size() * 8))) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  pl->miss_built = true;
+  return TEMX_OK;
+}
+
+// temx_tem_run in missing-value mode: two reads of the four fields, per-d masked systems, the shared epilogue
+static int miss_tem_run(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double* results, double* zonal, hipStream_t st) {
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  int rc;
+  if ((rc = miss_setup(pl))) return rc;
+  const int64_t D = pl->D, KD = (int64_t)pl->K * D, MD = (int64_t)pl->M * D;
+  if ((rc = pl->mB.ensure((size_t)(4 * KD + (int64_t)pl->NE * D) * 8))) return rc;
+  if ((rc = pl->mC.ensure((size_t)4 * pl->K4 * D * 8))) return rc;
+  if ((rc = pl->mCcov.ensure((size_t)pl->K4 * D * 8))) return rc;
+  if ((rc = pl->mcov.ensure((size_t)MD * 8))) return rc;
+  set_tail(pl, 0, pl->nt);
+  pl->miss_valid = false;
+  pl->op_valid = pl->os_valid = pl->c4_valid = pl->tq_valid = pl->xb_valid = false;
+  pl->miss_cov_D = -1;
+  const double* E = pl->mB.d() + 4 * KD;
+  TimedLaunch tl{};
+  time_begin(pl, 0, st, tl);
+  rc = launch_miss_project<4>(pl, fp, dtype, D, pl->colscale.d(), 2, pl->mB.d(), st);
+  time_end(pl, 0, st, tl);
+  if (rc) return rc;
+  // coefficients of u v theta omega, ub vb thetab wapb -> zb[0..3], coverage
+  if ((rc = launch_miss_system<4>(pl, pl->mB.d(), E, D, pl->mC.d(), pl->mCcov.d(), pl->zb.d(), pl->mcov.d(), st))) return rc;
+  TimedLaunch tl2{};
+  time_begin(pl, 1, st, tl2);
+  rc = launch_miss_eddy(pl, fp, dtype, st);
+  time_end(pl, 1, st, tl2);
+  if (rc) return rc;
+  const int slabs = pl->sp_eddy.nsplit * (8 / pl->sp_eddy.dpw);
+  if ((rc = launch_reduce(pl, pl->partial.d(), slabs, 3 * KD, pl->B3.d(), st))) return rc;
+  // upvpb upwappb vptpb -> zb[4..6] with the same systems
+  if ((rc = launch_miss_system<3>(pl, pl->B3.d(), E, D, nullptr, nullptr, pl->zb.d() + 4 * MD, nullptr, st))) return rc;
+  if ((rc = tem_epilogue(pl, results, zonal, st))) return rc;
+  pl->miss_valid = true;
+  pl->miss_cov_D = D;
+  return TEMX_OK;
+}
+
+// temx_zonal_mean in missing-value mode (the field's own finiteness is the mask)
+static int miss_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* out, int native, hipStream_t st) {
+  if (D < 1 || D >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "D must be in [1, 2^28)");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  HIPCHK(hipSetDevice(pl->device));
+  int rc;
+  if ((rc = miss_setup(pl))) return rc;
+  const int64_t KD = (int64_t)pl->K * D, MD = (int64_t)pl->M * D;
+  if ((rc = pl->opB.ensure((size_t)(KD + (int64_t)pl->NE * D) * 8))) return rc;
+  if ((rc = pl->mcov.ensure((size_t)MD * 8))) return rc;
+  pl->miss_cov_D = -1;
+  FieldPtrs<1> fp;
+  fp.p[0] = A;
+  if ((rc = launch_miss_project<1>(pl, fp, dtype, D, nullptr, -1, pl->opB.d(), st))) return rc;
+  const double* E = pl->opB.d() + KD;
+  if (!native) {
+    if ((rc = launch_miss_system<1>(pl, pl->opB.d(), E, D, nullptr, nullptr, out, pl->mcov.d(), st))) return rc;
+  } else {
+    if ((rc = pl->opC.ensure((size_t)2 * pl->K4 * D * 8))) return rc;
+    if ((rc = pl->mZ.ensure((size_t)MD * 8))) return rc;
+    double* C = pl->opC.d();
+    double* Ccov = C + (int64_t)pl->K4 * D;
+    if ((rc = launch_miss_system<1>(pl, pl->opB.d(), E, D, C, Ccov, pl->mZ.d(), pl->mcov.d(), st))) return rc;
+    if ((rc = launch_miss_native(pl, A, dtype, D, C, Ccov, out, st))) return rc;
+  }
+  pl->miss_cov_D = D;
+  return TEMX_OK;
+}
+
 int temx_tem_run(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                  int dtype, double* results, double* zonal, void* stream) try {
   int rc = tem_ready(pl);
   if (rc) return rc;
+  if (miss_mode(pl)) {
+    if (!ua || !va || !ta || !wap || !results) return fail(TEMX_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(pl->device));
+    return miss_tem_run(pl, four(ua, va, ta, wap), dtype, results, zonal, S_(stream));
+  }
   if (os_active(pl, dtype)) {
     if ((rc = os_ready(pl))) return rc;
     if (!ua || !va || !ta || !wap || !results) return fail(TEMX_EINVAL, "null argument");
@@ -3248,6 +3558,10 @@ int temx_tem_eddy(temx_plan* pl, const void* ua, const void* va, const void* ta,
   if (!tail_is_whole(pl)) return fail(TEMX_ESTATE, "the plan holds the coefficients of a time slice (temx_tem_os_tail), not of the whole run");
   EddyOut eo;
   for (int i = 0; i < TEMX_NEDDY; ++i) eo.p[i] = eddy_ptrs_host[i];
+  if (miss_mode(pl)) {
+    if (!pl->miss_valid) return fail(TEMX_ESTATE, "missing-value mode: the eddies need a masked temx_tem_run on this plan first");
+    return launch_miss_eddy_native(pl, four(ua, va, ta, wap), dtype, 0, pl->N, eo, S_(stream));
+  }
   if (unfused_stage2(pl)) {
     if ((rc = ensure_xb(pl, S_(stream)))) return rc;
     return launch_eddy_from_xbar(pl, four(ua, va, ta, wap), dtype, native_means(pl, 0, 1, 2, 3),
@@ -3268,6 +3582,12 @@ int temx_tem_eddy_rows(temx_plan* pl, const void* ua, const void* va, const void
   HIPCHK(hipSetDevice(pl->device));
   if (!tail_is_whole(pl)) return fail(TEMX_ESTATE, "the plan holds the coefficients of a time slice (temx_tem_os_tail), not of the whole run");
   hipStream_t st = S_(stream);
+  if (miss_mode(pl)) {
+    if (!pl->miss_valid) return fail(TEMX_ESTATE, "missing-value mode: the eddies need a masked temx_tem_run on this plan first");
+    EddyOut eo;
+    for (int i = 0; i < TEMX_NEDDY; ++i) eo.p[i] = eddy_ptrs_host[i];
+    return launch_miss_eddy_native(pl, four(ua, va, ta, wap), dtype, row0, nrows, eo, st);
+  }
   const int64_t D = pl->D, nd = nrows * D;
   // native zonal means of the rows (coefficients of the last temx_tem_stage2), then elementwise eddies
   DevBuf& ws = pl->opC;                       // operator-API workspace doubles as the row-chunk buffer
@@ -3299,6 +3619,7 @@ static int tracer_ws(temx_plan* pl) {
 }
 
 int temx_tracer_stage1(temx_plan* pl, const void* q, int dtype, double* Bq, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage1");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!q || !Bq) return fail(TEMX_EINVAL, "null argument");
@@ -3318,6 +3639,7 @@ int temx_tracer_stage1(temx_plan* pl, const void* q, int dtype, double* Bq, void
 
 int temx_tracer_stage2(temx_plan* pl, const void* q, const void* va, const void* wap, int dtype,
                        const double* Bq, double* Bq2, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage2");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!q || !va || !wap || !Bq || !Bq2) return fail(TEMX_EINVAL, "null argument");
@@ -3352,6 +3674,7 @@ int temx_tracer_stage2(temx_plan* pl, const void* q, const void* va, const void*
 } TEMX_CATCH
 
 int temx_tracer_stage3(temx_plan* pl, const double* Bq2, double* tres, double* tzon, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage3");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!Bq2 || !tres) return fail(TEMX_EINVAL, "null argument");
@@ -3379,6 +3702,7 @@ static inline bool tracer_one_pass(const temx_plan* pl) { return pl->cls && pl->
 
 int temx_tracer_stage1_sums(temx_plan* pl, const void* q, const void* va, const void* wap, int dtype,
                             double* Bq, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage1_sums");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!q || !va || !wap || !Bq) return fail(TEMX_EINVAL, "null argument");
@@ -3402,6 +3726,7 @@ int temx_tracer_stage1_sums(temx_plan* pl, const void* q, const void* va, const 
 } TEMX_CATCH
 
 int temx_tracer_stage2_from_sums(temx_plan* pl, const double* Bq, double* Bq2, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage2_from_sums");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!Bq || !Bq2) return fail(TEMX_EINVAL, "null argument");
@@ -3429,6 +3754,7 @@ int temx_tracer_stage2_from_sums(temx_plan* pl, const double* Bq, double* Bq2, v
 // temx_tracer_stage1_sums.
 int temx_tem_tracer_stage1(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                            const void* q, int dtype, double* B4, double* Bq, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_tracer_stage1");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !q || !B4 || !Bq) return fail(TEMX_EINVAL, "null argument");
@@ -3467,6 +3793,7 @@ int temx_tem_tracer_stage1(temx_plan* pl, const void* ua, const void* va, const 
 int temx_tem_tracer_run(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                         const void* q, int dtype, double* results, double* zonal, double* tres, double* tzon,
                         void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tem_tracer_run");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!q || !tres) return fail(TEMX_EINVAL, "null argument");
@@ -3485,6 +3812,7 @@ int temx_tem_tracer_run(temx_plan* pl, const void* ua, const void* va, const voi
 
 int temx_tracer_run(temx_plan* pl, const void* q, const void* va, const void* wap, int dtype,
                     double* tres, double* tzon, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_run");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (pl->os_valid && pl->c4_valid && tail_is_whole(pl) && os_active(pl, dtype)) {   // after a single-sweep TEM run: the tracer's single sweep
@@ -3515,6 +3843,7 @@ int temx_tracer_run(temx_plan* pl, const void* q, const void* va, const void* wa
 // -- and a last odd one alone; on any other path one temx_tracer_run after the other.
 int temx_tracers_run(temx_plan* pl, int nq, const void* const* q_host, const void* va, const void* wap, int dtype,
                      double* const* tres_host, double* const* tzon_host, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracers_run");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (nq < 1 || !q_host || !tres_host) return fail(TEMX_EINVAL, "bad argument");
@@ -3537,6 +3866,7 @@ int temx_tracers_run(temx_plan* pl, int nq, const void* const* q_host, const voi
 
 int temx_tracer_eddy(temx_plan* pl, const void* q, const void* va, const void* wap, int dtype,
                      double* const* ptrs3_host, void* stream) try {
+  if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_eddy");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!q || !va || !wap || !ptrs3_host) return fail(TEMX_EINVAL, "null argument");
@@ -3561,7 +3891,7 @@ int temx_status(temx_plan* pl, int* nonfinite, void* stream) try {
   HIPCHK(hipStreamSynchronize(S_(stream)));
   int f = 0;
   HIPCHK(hipMemcpy(&f, pl->flag.p, sizeof(int), hipMemcpyDeviceToHost));
-  *nonfinite = f;
+  *nonfinite = miss_mode(pl) ? 0 : f;     // missing-value mode: non-finite input is data, not an error
   if (f) {
     int zero = 0;
     HIPCHK(hipMemcpy(pl->flag.p, &zero, sizeof(int), hipMemcpyHostToDevice));

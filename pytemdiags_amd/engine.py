@@ -76,12 +76,30 @@ class Plan:
         return self.one_pass and self.option(_lib.OPT_TRACER_ONE_PASS) == 1
 
     def configure(self, form=None, os_map=None, op_map=None, os_subsample=None, tracer_one_pass=None,
-                  single_sweep_min_groups=None, os_contract=None):
+                  single_sweep_min_groups=None, os_contract=None, missing=None, min_coverage=None,
+                  missing_weight=None):
         """Path selection (temx_plan_configure); ``set_tem`` must follow.  ``form``: a key of ``_lib.FORMS``
         ("auto", "two-pass", "class-sums", "single-sweep", "no-single-sweep"); ``os_map`` / ``op_map``:
-        "row" or "tile" (lane map of the loads of the single sweep / of sweep 1 of the class-sum form)."""
+        "row" or "tile" (lane map of the loads of the single sweep / of sweep 1 of the class-sum form).
+        ``missing``: "raise" (default) or "mask" -- non-finite values are missing points of a masked fit
+        (include/temx.h, missing-value mode); ``min_coverage`` in [0, 1] (outputs whose coverage is below it are
+        NaN, 0 disables; default 0.5); ``missing_weight`` tau, a power of ten in [1e-14, 1e-4] (default 1e-10)."""
         def put(opt, val):
             check(self.lib.temx_plan_configure(self._h, opt, int(val)))
+        if missing is not None:
+            if missing not in _lib.MISSING_MODES:
+                raise ValueError("missing must be 'raise' or 'mask', got %r" % (missing,))
+            put(_lib.OPT_MISSING, _lib.MISSING_MODES[missing])
+        if min_coverage is not None:
+            mc = float(min_coverage)
+            if not 0.0 <= mc <= 1.0:
+                raise ValueError("min_coverage must lie in [0, 1], got %r" % (min_coverage,))
+            put(_lib.OPT_MIN_COVERAGE, int(round(mc * 1000)))
+        if missing_weight is not None:
+            e = -np.log10(float(missing_weight))
+            if not (float(missing_weight) > 0 and abs(e - round(e)) < 1e-9 and 4 <= round(e) <= 14):
+                raise ValueError("missing_weight must be 10^-n with n in 4..14, got %r" % (missing_weight,))
+            put(_lib.OPT_MISSING_WEIGHT, int(round(e)))
         if form is not None:
             put(_lib.OPT_FORM, _lib.FORMS[form] if isinstance(form, str) else form)
         for opt, val in ((_lib.OPT_OS_MAP, os_map), (_lib.OPT_OP_MAP, op_map)):
@@ -99,6 +117,19 @@ class Plan:
 
     def option(self, opt):
         return int(self.lib.temx_plan_option(self._h, int(opt)))
+
+    @property
+    def missing(self):
+        """"raise" or "mask" (missing-value mode, see :meth:`configure`)."""
+        return "mask" if self.option(_lib.OPT_MISSING) == 1 else "raise"
+
+    def coverage(self):
+        """Zonal-grid coverage ``[M][D]`` (device, fp64) of the latest masked run on this plan (``tem_run`` or
+        ``zonal_mean`` in missing-value mode): the default operator applied to the validity indicator."""
+        D = getattr(self, "_cov_D", None) or self.D or 1
+        out = torch.empty((self.M, D), dtype=torch.float64, device=self.device)
+        check(self.lib.temx_get_matrix(self._h, _lib.MAT_COVERAGE, _ptr(out), self._stream()))
+        return out
 
     # ---- lifetime ----
     def close(self):
@@ -178,6 +209,7 @@ class Plan:
                           device=self.device)
         check(self.lib.temx_zonal_mean(self._h, _ptr(A), _DT[A.dtype], D, _ptr(out), 1 if native else 0,
                                        self._stream()))
+        self._cov_D = D
         return out
 
     def zonal_mean_from_sums(self, B, trailing_shape, native=False):
@@ -218,6 +250,7 @@ class Plan:
         res, zon = out if out is not None else self._alloc_results(want_zonal)
         check(self.lib.temx_tem_run(self._h, _ptr(u), _ptr(v), _ptr(t), _ptr(w), dt, _ptr(res),
                                     _ptr(zon) if zon is not None else None, self._stream()))
+        self._cov_D = self.D
         return res, zon
 
     # ---- the single sweep in three steps (ncol-sharded jobs exchange between them; include/temx.h) ----

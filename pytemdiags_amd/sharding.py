@@ -120,6 +120,10 @@ class NcolShardedTEM:
     ``tail``: "auto" (sliced when possible), "replicated", or "sliced" (raise when not possible)."""
 
     def __init__(self, backend, group=None, tail="auto"):
+        if getattr(backend, "missing", "raise") == "mask":
+            raise NotImplementedError("NcolShardedTEM: missing-value mode (missing='mask') needs the whole grid in one "
+                                      "plan (the masked systems are per column of the zonal sums); use TimeShardedTEM "
+                                      "or one plan per process")
         self.backend = backend
         self.group = group
         self.world = _world(group)

@@ -45,8 +45,16 @@ class sph_zonal_averager:
 
     def __init__(self, lat, lat_out, L, weights=None, grid_name=None, grid_out_name=None,
                  ncoldim="ncol", overwrite=False, save_dest=None, debug=False, logfile=None,
-                 device=None, fp32_fields=False):
+                 device=None, fp32_fields=False, missing="raise", min_coverage=0.5):
         self.L = L
+        # (not in the reference's signature) missing="mask": non-finite values are missing points of a masked fit
+        # instead of an error; outputs whose coverage is below min_coverage are NaN (include/temx.h)
+        if missing not in _lib.MISSING_MODES:
+            raise ValueError("missing must be 'raise' or 'mask', got %r" % (missing,))
+        if not 0.0 <= float(min_coverage) <= 1.0:
+            raise ValueError("min_coverage must lie in [0, 1], got %r" % (min_coverage,))
+        self.missing = missing
+        self.min_coverage = float(min_coverage)
         # (not in the reference's signature) the arrays to be averaged are fp32: latitudes that agree to 1e-8 degrees
         # share a basis row (include/temx.h, TEMX_LAT_TOL_F32)
         self._fp32_fields = bool(fp32_fields)
@@ -160,6 +168,8 @@ class sph_zonal_averager:
                                  fp32_fields=self._fp32_fields)
         if weighted:
             self._plan.set_weights(self._w_raw)
+        if self.missing == "mask":
+            self._plan.configure(missing="mask", min_coverage=self.min_coverage)
         if cached is not None:
             # the engine applies its own factorisation of the same operator (built above for THIS grid, L and
             # weights); a cache is accepted only if it describes them too.  Quadrature weights do not make

@@ -35,7 +35,18 @@ class TEMDiagnostics:
     def __init__(self, ua, va, ta, wap, lat_native, q=None, p0=P0, zm_dlat=1, L=50,
                  dim_names=DEFAULT_DIMS, grid_name=None, zm_grid_name=None, map_save_dest=None,
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
-                 *, plev=None, time=None, dims=None, device=None):
+                 *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5):
+        # ---- missing-value mode (not in the reference): checked before anything touches the device ----
+        if missing not in ("raise", "mask"):
+            raise ValueError("missing must be 'raise' or 'mask', got %r" % (missing,))
+        if not 0.0 <= float(min_coverage) <= 1.0:
+            raise ValueError("min_coverage must lie in [0, 1], got %r" % (min_coverage,))
+        if missing == "mask" and q is not None:
+            raise NotImplementedError("missing='mask' does not support tracers (q=): a masked tracer would need a "
+                                      "mask of its own; fill or drop the tracer's missing values, or run it "
+                                      "separately with missing='raise'")
+        self.missing = missing
+        self.min_coverage = float(min_coverage)
         # ---- arguments (tem_diagnostics.py:217-236) ----
         self.p0 = p0
         self.q = q
@@ -62,7 +73,8 @@ class TEMDiagnostics:
         self.ZM = sph_zonal_averager(self._lat_native_np, self._lat_zm, self.L, grid_name=grid_name,
                                      grid_out_name=zm_grid_name, save_dest=map_save_dest,
                                      debug=debug_level > 1, overwrite=overwrite_map, device=self._device,
-                                     fp32_fields=str(self._work_dtype) == "torch.float32")
+                                     fp32_fields=str(self._work_dtype) == "torch.float32",
+                                     missing=missing, min_coverage=self.min_coverage)
         if self.ZM.Y0 is None or self.ZM.Y0p is None:
             self.ZM.sph_compute_matrices(overwrite=overwrite_map)
         self._zonal_mean = self.ZM.sph_zonal_mean
@@ -77,6 +89,8 @@ class TEMDiagnostics:
             self._res, self._zon, *fused = plan.tem_tracer_run(*self._dev_fields, self._dev_q[0], want_zonal=True)
         else:
             self._res, self._zon = plan.tem_run(*self._dev_fields, want_zonal=True)
+        # missing="mask": coverage of this run on the zonal grid (the averager's later calls reuse the plan)
+        self._cov = plan.coverage().reshape(self.ZM_N, self.NLEV, self.NT) if missing == "mask" else None
         if plan.status():                                   # sph_zonal_mean.py:219-221
             raise RuntimeError("Variable has nans! Spectral zonal averager cannot handle nans; "
                                "please replace or remove them")
@@ -284,6 +298,14 @@ class TEMDiagnostics:
 
     # ---- getters (tem_diagnostics.py:412-487) ----
     ub = property(lambda s: s._zonal("ub", "ua"))
+
+    @property
+    def coverage(self):
+        """missing="mask": the spectral zonal-mean valid fraction of the run on the zonal grid (labelled like
+        ``ub``, float64); outputs are NaN where it is below ``min_coverage``.  None in the default mode."""
+        if self._cov is None:
+            return None
+        return self._wrap(self._cov, "coverage", "ua", force64=True)
     vb = property(lambda s: s._zonal("vb", "va"))
     thetab = property(lambda s: s._zonal("thetab", "ta"))
     wapb = property(lambda s: s._zonal("wapb", "wap"))
