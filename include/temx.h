@@ -54,7 +54,11 @@ enum {
                             temx_plan_finalize).  TEMX_NO_QR=0/1 in the environment overrides */
   TEMX_LAT_TOL_F32 = 16  /* the fields will be fp32 (results compared to ~1e-5): latitudes are matched to 1e-8 degrees
                             instead of 1e-11 when latitude classes / mirror pairs are looked for, so that grids
-                            whose latitude coordinate carries more noise keep the class sweeps (error ~ L x tol) */
+                            whose latitude coordinate carries more noise keep the class sweeps (error ~ L x tol);
+                            and a latitude class with more than 16 members on a side is cut (a lat-lon row into
+                            classes of 8 + 8, the shape of a cubed sphere's), because the single sweep of fp32 fields
+                            sums a side in fp32.  Without the flag that sweep refuses fp32 fields on a plan with a
+                            side of more than 64 members (TEMX_EUNSUPPORTED) */
 };
 
 /* Path selection (temx_plan_configure; takes effect at the next temx_plan_set_tem, which must follow).  The
@@ -117,13 +121,15 @@ enum {
 enum {
   TEMX_MAT_Y0 = 0,    /* [N][K]   sph_zonal_mean.py:360-363 */
   TEMX_MAT_Y0P = 1,   /* [M][K]   sph_zonal_mean.py:367-370 */
-  TEMX_MAT_GRAM = 2,  /* [K][K]   Y0^T Y0 (this rank's rows only until finalised with a global G) */
+  TEMX_MAT_GRAM = 2,  /* [K][K]   Y0^T Y0 over this rank's rows (also after temx_plan_finalize with the job's G: a
+                                  second all-reduce of it gives the job's matrix again) */
   TEMX_MAT_GINV = 3,  /* [K][K]   inverse Gram; Y0inv = GINV . Y0^T */
   TEMX_MAT_Y0INV = 4, /* [K][N]   pinv(Y0) as the reference stores it, sph_zonal_mean.py:389 */
   TEMX_MAT_GRAM2 = 5, /* [K][K]   Q^T Q over this rank's rows, Q = Y0 R^-1 the basis the finalised plan projects
                                   on (see temx_plan_finalize); the identity if the plan keeps the Y0 basis */
   TEMX_MAT_GX = 6,    /* [K][2L+1] Y0^T Y0ext over this rank's rows, Y0ext = Y_l^0 up to degree 2L (single sweep;
-                                  after temx_plan_set_tem on a plan with temx_plan_single_sweep() == 1) */
+                                  after temx_plan_set_tem on a plan with temx_plan_single_sweep() == 1); it stays
+                                  this rank's own matrix after temx_plan_set_os_matrices */
   TEMX_MAT_GSUB = 7,  /* [KR][KR] Gram matrix of the first KR = min(16, K) harmonics over this rank's share of the
                                   reference subsample (single sweep) */
   TEMX_MAT_COVERAGE = 8 /* [M][D] zonal-grid coverage of the latest masked run on this plan (TEMX_ESTATE before one) */

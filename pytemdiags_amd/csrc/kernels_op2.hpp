@@ -1113,10 +1113,16 @@ sweep_os2_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
 #pragma unroll
     for (int t = 0; t < TBX; ++t) ax[f][t] = 0.0;
   // fp32 inputs: the sums of a class side about its first member, S~ = sum (x - x0) and q~ = sum (a - a0)(b - b0), are
-  // accumulated in fp32 (TEMX_OS2_ACC32).  The differences are eddy-sized and a side has 8 members on a cubed sphere:
-  // the rounding of these sums is ~1e-7 of the EDDY amplitude, four orders below the 2e-5 the fp32 path is held to
-  // (the reference's own fp32-input run differs from its fp64 run by 5e-6), and everything from the side
-  // means on is fp64 as before.  It takes the conversions and the quarter-rate fp64 VALU work out of the inner loop.
+  // accumulated in fp32 (TEMX_OS2_ACC32), member after member.  The differences are eddy-sized, amplitude A: after k
+  // members the partial sum is <= k A and the k-th addition rounds by <= k A 2^-24, so a side of n members leaves
+  // S~ / n off by <= n 2^-25 A (q~ / n likewise in units of A^2), n 2^-24 with the rounding of the differences
+  // themselves.  A tenth of the 2e-5 the fp32 path is held to (the reference's own fp32-input run
+  // differs from its fp64 run by 5e-6) allows n <= 2e-6 x 2^24 = 33 -- in units of the eddy amplitude; a flux mean
+  // is compared in units of the flux, a tenth of A^2 for waves in quadrature, which takes the side to the 8 members
+  // of a cubed sphere (n 2^-24 = 4.8e-7; measured 5e-6 of the flux): the host cuts the long class sides of an fp32
+  // plan to TEMX_F32_SIDE_CAP = 8 members (temx.hip, above build_classes, with the measurements) and this kernel is
+  // not launched on a table with a side beyond 8 x that.  Everything from the side means on is fp64 as before.  It
+  // takes the conversions and the quarter-rate fp64 VALU work out of the inner loop.
   using AT = typename std::conditional<(sizeof(T) == 4 && TEMX_OS2_ACC32), float, double>::type;
   AT s[NF], q[NP], x0[NF], cnt = 0;
 #pragma unroll

@@ -131,6 +131,7 @@ struct temx_plan {
   // latitude-class path (columns sharing a latitude share a basis row), see kernels_cls.hpp
   bool cls = false;
   int64_t cgroups = 0, cbatches = 0, ncls = 0;
+  int64_t cls_max_side = 0;            // members of the longest class side (build_classes; TEMX_F32_SIDE_CAP)
   std::vector<int> gbatch0;            // first batch of every class-group (+ total)
   DevBuf crow, ycls;
   std::map<int, DevBuf> csplits;       // work cuts per number of pieces
@@ -145,6 +146,8 @@ struct temx_plan {
   std::vector<int> sgbatch0;           // subsample of class-groups (reference pre-pass): first batch of each (+ total)
   int64_t sgroups = 0, sbatches = 0;
   DevBuf ycx, ycx_s, crow_s, rho, rho0, gaunt /* Yq[NQ][KX] */, wq2, Gx, Gsinv, Ax /* [4 KX + 3 K][D]: projections of the fields, then of the products */, Axs /* [4][KR][D] */;
+  std::vector<double> h_G_own;         // Y0^T Y0 over this rank's rows, kept when temx_plan_finalize installs the job's matrix
+  std::vector<double> h_Gx_own;        // Gx over this rank's rows, as built: what temx_get_matrix(TEMX_MAT_GX) hands out
   std::vector<double> h_Gx, h_Gs;      // this plan's rows: Y0^T Y0ext [K][KX] and the subsample's Gram matrix [KR][KR] (all-reduced when ncol-sharded)
   // contraction of the single sweep on the matrix cores (kernels_osc.hpp): host copies of its matrices, their 4x4
   // blocks on the device (one buffer), the synthesised fields At / ab [4][NQ][D] (kept: the tracer pairs with v, omega)
@@ -673,9 +676,32 @@ struct ClassTables {
   std::vector<int> gbatch0;     // [ngroups + 1]
   std::vector<double> cnt;      // [ngroups][2 sides][4 classes] member counts
   int64_t ncls = 0, ngroups = 0, nbatch = 0;
+  int64_t max_side = 0;         // members of the longest class side
 };
 
-static bool build_classes(const double* lat, int64_t N, ClassTables& ct, double tol_dflt) {
+// Longest class side of a plan for fp32 fields (TEMX_LAT_TOL_F32).  sweep_os2_kernel adds the members of a side into
+// ONE fp32 accumulator in sequence: with terms of size <= A (the eddy amplitude) the partial sum after k members is
+// <= k A and the k-th addition rounds by <= k A 2^-24, so the sum of n members is off by <= A 2^-24 n^2 / 2 and the
+// side mean S~ / n (and likewise q~ / n in units of A^2) by <= n 2^-25 -- call it n 2^-24 with the rounding of the
+// differences themselves.  The fp32 path is held to 2e-5 of the field maximum; a tenth of that, 2e-6, allows
+// n <= 2e-6 x 2^24 = 33.  But the bound is in units of the eddy AMPLITUDE, and a flux mean is normalised by the
+// flux: with waves in quadrature (u' ~ sin 4 lon, v' ~ cos 4 lon, the fields of the test suite) max |u'v' mean| is
+// about A^2 / 10, and a part of a lat-lon row spans enough longitude for the whole wave to enter its sums.  Sides
+// of 32 measured 1.6e-5 ... 2.5e-5 of max |u'v' mean| on rows of 352 and 360 columns, sides of 8 -- the side of a
+// cubed sphere, whose members lie all around the globe -- 5e-6.  Hence parts of 8: n 2^-24 = 4.8e-7, forty times
+// under 2e-5 in units of A^2 and four times under it in the unit the results are compared in; two whole batches.
+// A side of up to TEMX_F32_SIDE_KEEP = 16 members is left whole: at the 1e-8 degrees of an fp32 plan five pairs of
+// neighbouring latitudes of ne240 fall into one class of 16 + 16, and the class tables of the cubed spheres that are
+// timed (ne30, ne120, ne240) stay as they were, bit for bit.
+#ifndef TEMX_F32_SIDE_CAP
+#define TEMX_F32_SIDE_CAP 8
+#endif
+#ifndef TEMX_F32_SIDE_KEEP
+#define TEMX_F32_SIDE_KEEP 16
+#endif
+
+static bool build_classes(const double* lat, int64_t N, ClassTables& ct, double tol_dflt, size_t side_cap = 0,
+                          size_t side_keep = 0) {
   if (N >= ((int64_t)1 << 27) || N < 64) return false;     // row indices live in 27 bits of a table entry
   const double tol = sym_tol_deg(tol_dflt);
   std::vector<int> order((size_t)N);
@@ -745,6 +771,36 @@ static bool build_classes(const double* lat, int64_t N, ClassTables& ct, double 
     }
     cls.swap(out);
   }
+  // fp32 plans: a side longer than side_keep members is cut into parts of side_cap (TEMX_F32_SIDE_CAP above).  A
+  // lat-lon, Gaussian or HEALPix-like grid has NLON members per side and NLON is the TYPICAL size there, so the cut
+  // above leaves them whole.  Each part is a class of its own at the same latitude, with its own first member as the
+  // origin of its sums.  Classes within side_keep -- every class of a cubed sphere from ne8 on, whose equator the cut
+  // above already took to 8 + 8 -- are not touched, and the order of the others among them is kept: a table without
+  // a long side comes out bit for bit as before.
+  if (side_cap) {
+    bool any = false;
+    for (const Cls& c : cls) any = any || c.n.size() > side_keep || c.s.size() > side_keep;
+    if (any) {
+      std::vector<Cls> out;
+      out.reserve(cls.size());
+      for (Cls& c : cls) {
+        if (c.n.size() <= side_keep && c.s.size() <= side_keep) {
+          out.push_back(std::move(c));
+          continue;
+        }
+        const size_t parts = (std::max(c.n.size(), c.s.size()) + side_cap - 1) / side_cap;
+        for (size_t k = 0; k < parts; ++k) {
+          Cls d;
+          d.alat = c.alat;
+          for (size_t m = k * side_cap; m < std::min((k + 1) * side_cap, c.n.size()); ++m) d.n.push_back(c.n[m]);
+          for (size_t m = k * side_cap; m < std::min((k + 1) * side_cap, c.s.size()); ++m) d.s.push_back(c.s[m]);
+          out.push_back(std::move(d));
+        }
+      }
+      cls.swap(out);
+    }
+  }
+  for (const Cls& c : cls) ct.max_side = std::max<int64_t>(ct.max_side, (int64_t)std::max(c.n.size(), c.s.size()));
   // equal member counts inside a class-group; then by first row (some streaming order)
   std::stable_sort(cls.begin(), cls.end(), [&](const Cls& a, const Cls& b) {
     const int an = nb(a.n.size()), as = nb(a.s.size()), bn = nb(b.n.size()), bs = nb(b.s.size());
@@ -1652,6 +1708,7 @@ static int build_os_tables(temx_plan* pl) {
     for (int t = 0; t < nth; ++t)          // fixed order: the same bits whatever the scheduling
       for (size_t i = 0; i < Gx.size(); ++i) Gx[i] += part[(size_t)t][i];
     if ((rc = upload(pl->Gx, Gx.data(), Gx.size() * 8))) return rc;
+    pl->h_Gx_own = Gx;
     pl->h_Gx = std::move(Gx);
   }
   pl->os_built = true;
@@ -1736,6 +1793,10 @@ static int launch_sweep_os_t(temx_plan* pl, const FieldPtrs<4>& fp, bool sub, co
       break;                                                                                                        \
     }                                                                                                               \
     if (sizeof(T) == 4) {   /* fp32 inputs: two waves per SIMD (kernels_op2.hpp, sweep_os2_kernel) */              \
+      if (pl->cls_max_side > 8 * TEMX_F32_SIDE_CAP)                                                                 \
+        return fail(TEMX_EUNSUPPORTED, "single sweep of fp32 fields: a latitude class of this plan has %lld members on one " \
+                    "side, and the sweep sums a side in fp32; create the plan with TEMX_LAT_TOL_F32",               \
+                    (long long)pl->cls_max_side);                                                                   \
       auto kern = sweep_os2_kernel<float, TBSv, TBXv, NBR, 2, KIND>;                                                \
       const size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +                      \
                           (size_t)8 * (KD::NP - KD::NPR) * TBSv * 64 + (size_t)(KD::NF + KD::NP) * 512) * 8;        \
@@ -2362,7 +2423,8 @@ int temx_plan_create(temx_plan** out, int device, int64_t ncol, int L, int M,
     const char* e1 = getenv("TEMX_NO_CLS");
     ClassTables ct;
     if ((!pl->large || pl->K <= 256) && !(flags & (TEMX_NO_SYMMETRY | TEMX_NO_CLASSES)) && !(e0 && e0[0] == '1') &&
-        !(e1 && e1[0] == '1') && build_classes(lat_deg_host, ncol, ct, tol_dflt)) {
+        !(e1 && e1[0] == '1') &&
+        build_classes(lat_deg_host, ncol, ct, tol_dflt, (flags & TEMX_LAT_TOL_F32) ? (size_t)TEMX_F32_SIDE_CAP : 0, TEMX_F32_SIDE_KEEP)) {
       if ((rc = upload(pl->crow, ct.crow.data(), ct.crow.size() * sizeof(int)))) return bail(rc);
 
       if ((rc = upload(pl->ccnt, ct.cnt.data(), ct.cnt.size() * 8))) return bail(rc);
@@ -2384,6 +2446,7 @@ int temx_plan_create(temx_plan** out, int device, int64_t ncol, int L, int M,
       pl->cgroups = ct.ngroups;
       pl->cbatches = ct.nbatch;
       pl->ncls = ct.ncls;
+      pl->cls_max_side = ct.max_side;
       if (pl->large) {   // class sums first, sliced basis at the class latitudes (kernels_cls.hpp)
         pl->ycls_lstride = (ct.ngroups + 1) * 256;
         if ((rc = pl->ycls_l.ensure((size_t)pl->nslice * pl->ycls_lstride * 8))) return bail(rc);
@@ -2476,6 +2539,10 @@ int temx_plan_finalize(temx_plan* pl, const double* G_host) try {
   const int K = pl->K;
   std::vector<double> G((size_t)K * K), Gi((size_t)K * K);
   if (G_host) {
+    if (pl->h_G_own.empty()) {    // TEMX_MAT_GRAM stays this rank's own sums (a second runner all-reduces them again)
+      pl->h_G_own.resize((size_t)K * K);
+      HIPCHK(hipMemcpy(pl->h_G_own.data(), pl->G.p, G.size() * 8, hipMemcpyDeviceToHost));
+    }
     std::copy(G_host, G_host + (size_t)K * K, G.begin());
     HIPCHK(hipMemcpy(pl->G.p, G.data(), G.size() * 8, hipMemcpyHostToDevice));
   } else {
@@ -2626,6 +2693,11 @@ int temx_get_matrix(temx_plan* pl, int which, double* dst, void* stream) try {
       HIPCHK(hipMemcpyAsync(dst, pl->Y0p.p, (size_t)pl->M * pl->K * 8, hipMemcpyDeviceToDevice, st));
       return TEMX_OK;
     case TEMX_MAT_GRAM:
+      if (!pl->h_G_own.empty()) {       // finalised with the job's matrix: pl->G holds that one
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(dst, pl->h_G_own.data(), KK, hipMemcpyHostToDevice));
+        return TEMX_OK;
+      }
       HIPCHK(hipMemcpyAsync(dst, pl->G.p, KK, hipMemcpyDeviceToDevice, st));
       return TEMX_OK;
     case TEMX_MAT_GINV:
@@ -2656,7 +2728,9 @@ int temx_get_matrix(temx_plan* pl, int which, double* dst, void* stream) try {
     case TEMX_MAT_GX:
     case TEMX_MAT_GSUB: {
       if (!pl->os_built) return fail(TEMX_ESTATE, "the single-sweep tables are not built (temx_plan_set_tem on a plan that takes that form)");
-      const std::vector<double>& h = which == TEMX_MAT_GX ? pl->h_Gx : pl->h_Gs;
+      // this rank's own sums, whatever temx_plan_set_os_matrices has installed since: a second all-reduce of them
+      // (a second temx_plan_set_tem, a second runner on the plan) gives the job's matrix again, not a multiple of it
+      const std::vector<double>& h = which == TEMX_MAT_GX ? pl->h_Gx_own : pl->h_Gs;
       HIPCHK(hipStreamSynchronize(st));
       HIPCHK(hipMemcpy(dst, h.data(), h.size() * 8, hipMemcpyHostToDevice));
       return TEMX_OK;

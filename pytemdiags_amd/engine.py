@@ -39,6 +39,7 @@ class Plan:
         self.N, self.M, self.L, self.K = int(lat.size), int(lat_out.size), int(L), int(L) + 1
         self.lat_out = lat_out
         self.nlev = self.nt = self.D = None
+        self.form_requested = "auto"
         check(self.lib.temx_plan_create(C.byref(self._h), self.device_index, self.N, self.L, self.M,
                                         plat, plat_out, (_lib.DEFER_FINALIZE if defer_finalize else 0)
                                         | (0 if symmetry else _lib.NO_SYMMETRY)
@@ -102,6 +103,7 @@ class Plan:
             put(_lib.OPT_MISSING_WEIGHT, int(round(e)))
         if form is not None:
             put(_lib.OPT_FORM, _lib.FORMS[form] if isinstance(form, str) else form)
+            self.form_requested = form          # (temx_plan_option reports the form in effect, not the request)
         for opt, val in ((_lib.OPT_OS_MAP, os_map), (_lib.OPT_OP_MAP, op_map)):
             if val is not None:
                 put(opt, {"row": 0, "tile": 1}[val] if isinstance(val, str) else val)

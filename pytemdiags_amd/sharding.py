@@ -130,6 +130,8 @@ class NcolShardedTEM:
         self.rank = dist.get_rank(group) if self.world > 1 else 0
         self.tail = tail
         self._sliced = None                            # decided at the first step (the plan's TEM shape is set later)
+        self._shape = None                             # the backend's (nlev, nt) the decision was taken for
+        self._form_before = None                       # the backend's form, while this runner holds it off the single sweep
         self._buf = {}
         G = backend.matrix(MAT_GRAM)
         allreduce_sum_(G, group)                       # (i) Gram matrix, K x K, once
@@ -144,6 +146,10 @@ class NcolShardedTEM:
         the plan-build collectives of the time-sliced form.  (Calling ``backend.set_tem`` directly works too: the
         collectives then run at the first step.)"""
         be = self.backend
+        if self._form_before is not None:
+            # an earlier shape (nt < world) sent every rank to the class-sum form: the new shape decides afresh
+            be.configure(form=self._form_before)
+            self._form_before = None
         if hasattr(be, "configure") and self.tail != "replicated":
             # the subsample spread over the ranks; and the single sweep chosen by the size of the JOB: with a
             # time-sliced tail a rank contracts 1 / world of the columns, so the threshold scales with it
@@ -161,8 +167,10 @@ class NcolShardedTEM:
         if self.world > 1:
             dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
         self._sliced = bool(flag.item() > 0.5)
+        self._shape = (getattr(be, "nlev", None), getattr(be, "nt", None))
         if self._sliced:
-            # the two matrices of the single sweep that sum over the rows (temx_plan_set_os_matrices)
+            # the two matrices of the single sweep that sum over the rows (temx_plan_set_os_matrices); matrix() hands
+            # out this rank's own sums every time, so deciding again (a new shape, a second runner) installs the same
             Gx, Gs = be.matrix(MAT_GX), be.matrix(MAT_GSUB)
             allreduce_sum_(Gx, self.group)
             allreduce_sum_(Gs, self.group)
@@ -172,8 +180,10 @@ class NcolShardedTEM:
         elif bool(getattr(be, "single_sweep", False)):
             # some rank cannot: all ranks take the class-sum form (its stage interface is what the replicated flow drives)
             args = be.tem_args
+            self._form_before = getattr(be, "form_requested", "auto")
             be.configure(form="no-single-sweep")
             be.set_tem(*args)
+            self._shape = (be.nlev, be.nt)
         return self._sliced
 
     @property
@@ -202,8 +212,8 @@ class NcolShardedTEM:
 
     def run(self, ua, va, ta, wap, want_zonal=False):
         be = self.backend
-        if self._sliced is None:
-            self._decide()
+        if self._sliced is None or self._shape != (getattr(be, "nlev", None), getattr(be, "nt", None)):
+            self._decide()                             # first step, or backend.set_tem since: the time axis cuts anew
         if self._sliced:
             As = be.tem_os_prepass(ua, va, ta, wap, out=self._buffer("As", (4, be.KR, be.D)))
             allreduce_sum_(As, self.group)             # (ii) reference pre-pass sums [4][KR][D], one message

@@ -15,14 +15,16 @@ torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NE, NLEV, NT = 8, 12, 5          # D = 60: four d-tiles, the smallest shape the one-pass forms take
+REPLAN_NT = (NT, 7, 1, NT)       # the shapes of the "ncol-replan" mode, one runner.set_tem each (D = 60, 84, 12, 60)
+REPLAN_NT_MAX = 7
 
 
-def _inputs():
+def _inputs(nt=NT):
     from pytemdiags_amd import synth
     lat, lon = synth.cubed_sphere_gll(NE)
     plev = synth.pressure_levels(NLEV)
-    f = synth.analytic_fields(lat, lon, plev, NT, seed=21)
-    q = synth.analytic_tracer(lat, lon, plev, NT)
+    f = synth.analytic_fields(lat, lon, plev, nt, seed=21)
+    q = synth.analytic_tracer(lat, lon, plev, nt)
     lat_zm = (np.arange(-90, 91, 1.0)[1:] + np.arange(-90, 91, 1.0)[:-1]) / 2
     return lat, plev, f, q, lat_zm
 
@@ -36,7 +38,7 @@ def _worker(rank, world, port, mode, ret):
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        lat, plev, f, q, lat_zm = _inputs()
+        lat, plev, f, q, lat_zm = _inputs(REPLAN_NT_MAX if mode == "ncol-replan" else NT)
         dev = lambda x: torch.as_tensor(np.ascontiguousarray(x), device="cuda:0")   # noqa: E731
         if mode in ("ncol", "ncol-sliced"):
             mine = sharding.symmetric_ncol_shards(lat, world)[rank]
@@ -58,6 +60,37 @@ def _worker(rank, world, port, mode, ret):
                 assert res.shape[-1] == runner.my_snapshots()[1] - runner.my_snapshots()[0]
                 res, tres = sharding.gather_time(res), sharding.gather_time(tres)
             out = torch.cat([res, tres])
+            paired = plan.paired
+        elif mode == "ncol-replan":
+            # one plan per rank through a sequence of shapes and runners: [NT] sliced; [7] sliced again (the
+            # plan-build collectives a second time); [1] nt < world, so every rank leaves the single sweep for the
+            # replicated tail; [NT] back to the sliced tail; then a second runner on the same plan
+            mine = sharding.symmetric_ncol_shards(lat, world)[rank]
+            plan = engine.Plan(lat[mine], lat_zm, 50, defer_finalize=True, form="single-sweep")
+            runner = sharding.NcolShardedTEM(plan)
+            own_G = plan.matrix(sharding.MAT_GRAM).clone()
+            own_Gx, outs = None, []
+            for step, nt in enumerate(REPLAN_NT + (6,)):
+                if step == len(REPLAN_NT):
+                    runner = sharding.NcolShardedTEM(plan, tail="sliced")
+                    assert torch.equal(plan.matrix(sharding.MAT_GRAM), own_G)
+                runner.set_tem(NLEV, nt, plev * 100)
+                assert runner.sliced == (nt >= world), (nt, runner.sliced)
+                if runner.sliced:
+                    if own_Gx is None:
+                        own_Gx = plan.matrix(sharding.MAT_GX).clone()
+                    assert torch.equal(plan.matrix(sharding.MAT_GX), own_Gx)      # not the all-reduced matrix
+                res, _ = runner.run(*[dev(x[mine][:, :, :nt]) for x in f])
+                if runner.sliced:
+                    res = sharding.gather_time(res)
+                assert res.shape[-1] == nt
+                outs.append(res)
+            # backend.set_tem behind the runner's back: the time axis must be cut for the new shape at the next step
+            plan.set_tem(NLEV, REPLAN_NT_MAX, plev * 100)
+            res, _ = runner.run(*[dev(x[mine][:, :, :REPLAN_NT_MAX]) for x in f])
+            assert runner.my_snapshots() == sharding.shard_bounds(REPLAN_NT_MAX, world, rank)
+            outs.append(sharding.gather_time(res))
+            out = torch.cat(outs, dim=-1)
             paired = plan.paired
         else:
             plan = engine.Plan(lat, lat_zm, 50)
@@ -157,3 +190,59 @@ def test_bench_line_at_two_ranks_and_failure_exit_code():
     env["TEMX_BENCH_FAIL"] = "main"
     p = subprocess.run(cmd + ["--no-extras"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode != 0
+
+
+def test_set_tem_again_on_a_sharded_runner():
+    """runner.set_tem with a new nt (once with nt < world: the sliced decision flips, and flips back), a second
+    NcolShardedTEM on the same plan and a backend.set_tem between two steps: every run is the unsharded run on the
+    same fields.  The matrices a rank contributes to the plan-build all-reduces (TEMX_MAT_GRAM, TEMX_MAT_GX) must
+    stay its own, or the second all-reduce installs world x the job's matrix.  One time limit for the two children,
+    no second attempt."""
+    import torch.multiprocessing as mp
+    if any(os.environ.get(k) == "1" for k in ("TEMX_NO_SYM", "TEMX_NO_CLS", "TEMX_TWO_PASS", "TEMX_NO_QR")) or \
+            os.environ.get("TEMX_SINGLE_SWEEP") == "0":
+        pytest.skip("the environment forces another form of the sweeps: no single sweep, no time-sliced tail")
+    from pytemdiags_amd import engine
+    import queue
+    import time
+    lat, plev, f, q, lat_zm = _inputs(REPLAN_NT_MAX)
+    ctx = mp.get_context("spawn")
+    ret = ctx.Queue()
+    port = _port()
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, "ncol-replan", ret)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = None
+    try:
+        deadline = time.monotonic() + 300
+        while got is None and time.monotonic() < deadline:
+            try:
+                got, paired, bad = ret.get(timeout=2)
+            except queue.Empty:       # (a child that failed an assertion has nothing to send: do not wait it out)
+                if any(p.exitcode not in (None, 0) for p in procs):
+                    break
+    finally:
+        for p in procs:
+            p.join(timeout=120)
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+                p.join(timeout=30)
+    assert [p.exitcode for p in procs] == [0, 0] and got is not None
+    assert not bad
+    plan = engine.Plan(lat, lat_zm, 50)
+    refs = []
+    for nt in REPLAN_NT + (6, REPLAN_NT_MAX):
+        plan.set_tem(NLEV, nt, plev * 100)
+        r, _ = plan.tem_run(*[torch.as_tensor(np.ascontiguousarray(x[:, :, :nt]), device="cuda:0") for x in f])
+        refs.append(r.cpu().numpy())
+    plan.close()
+    ref = np.concatenate(refs, axis=-1)
+    assert got.shape == ref.shape
+    t0 = 0
+    for step, r in enumerate(refs):
+        t1 = t0 + r.shape[-1]
+        for i in range(r.shape[0]):
+            err = np.max(np.abs(got[i][..., t0:t1] - r[i])) / np.max(np.abs(r[i]))
+            assert err <= 1e-11, (step, r.shape[-1], i, err)
+        t0 = t1

@@ -156,6 +156,61 @@ def test_ncol_shards_with_time_sliced_tail_emulated_on_one_gpu(ne, nlev, nt, W):
         assert _relerr(tgot[i], tref[i]) <= 1e-11, n
 
 
+def test_set_tem_again_on_ncol_shards_emulated_on_one_gpu():
+    """The plan-build collectives of the sharded single sweep a second time on the same plans: a new shape
+    (temx_plan_set_tem with another nt), and once more at the first shape as a second runner on the plans would.
+    TEMX_MAT_GX and TEMX_MAT_GRAM are this rank's own sums before and after the job's matrices are installed
+    (temx_plan_set_os_matrices, temx_plan_finalize): were the installed matrix handed back, the second all-reduce
+    would install W x Gx and every eddy-flux result would be off by a term that scales with the world size."""
+    from pytemdiags_amd import _lib, engine, sharding
+    _skip_if_forced_elsewhere()
+    ne, nlev, L, W = 12, 8, 50, 2
+    nts = (9, 12, 9)              # D = 72, 96, 72
+    lat, lon, plev, f, q, lat_zm = _case(ne, nlev, max(nts))
+    whole = engine.Plan(lat, lat_zm, L, form="single-sweep")
+    shards = sharding.symmetric_ncol_shards(lat, W)
+    plans = [engine.Plan(lat[m], lat_zm, L, defer_finalize=True, form="single-sweep") for m in shards]
+    own_G = [p.matrix(_lib.MAT_GRAM).clone() for p in plans]
+    own_Gx = None
+    for step, nt in enumerate(nts):
+        fs = [np.ascontiguousarray(x[:, :, :nt]) for x in f]
+        whole.set_tem(nlev, nt, plev * 100)
+        ref, _ = whole.tem_run(*[_dev(x) for x in fs])
+        if step != 1:       # (a new shape alone keeps the finalised basis; a second runner finalises again)
+            G = sum(p.matrix(_lib.MAT_GRAM) for p in plans).cpu().numpy()
+            for p in plans:
+                p.finalize(G)
+            G2 = sum(p.matrix(_lib.MAT_GRAM2) for p in plans).cpu().numpy()
+            for p in plans:
+                p.refine(G2)
+        for p, g in zip(plans, own_G):
+            assert torch.equal(p.matrix(_lib.MAT_GRAM), g), "TEMX_MAT_GRAM changed by temx_plan_finalize"
+        for p in plans:
+            p.configure(os_subsample=12)
+            p.set_tem(nlev, nt, plev * 100)
+            assert p.single_sweep
+        if own_Gx is None:
+            own_Gx = [p.matrix(_lib.MAT_GX).clone() for p in plans]
+        Gx = sum(p.matrix(_lib.MAT_GX) for p in plans).cpu().numpy()
+        Gs = sum(p.matrix(_lib.MAT_GSUB) for p in plans).cpu().numpy()
+        for p, g in zip(plans, own_Gx):
+            p.set_os_matrices(Gx, Gs)
+            assert torch.equal(p.matrix(_lib.MAT_GX), g), "TEMX_MAT_GX changed by temx_plan_set_os_matrices"
+        loc = [[_dev(x[m]) for x in fs] for m in shards]
+        As = sum(p.tem_os_prepass(*x) for p, x in zip(plans, loc))
+        proj = sum(p.tem_os_sweep(*x, As, nslices=W) for p, x in zip(plans, loc))
+        outs = []
+        for w, p in enumerate(plans):
+            t0, t1 = sharding.shard_bounds(nt, W, w)
+            outs.append(p.tem_os_tail(proj[w], t0, t1 - t0)[0])
+            assert not p.status()
+        got = torch.cat(outs, dim=-1)
+        for i, n in enumerate(_lib.RESULT_NAMES):
+            assert _relerr(got[i], ref[i]) <= 1e-11, (step, nt, n, _relerr(got[i], ref[i]))
+    for p in plans + [whole]:
+        p.close()
+
+
 def test_nan_input_on_the_single_sweep_path():
     """SURVEY Q14 (sph_zonal_mean.py:219-221: NaN anywhere in an input raises) on the path the headline runs."""
     from pytemdiags_amd import engine

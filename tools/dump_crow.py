@@ -1,8 +1,11 @@
+"""Development aid: have the library write the row table of a cubed-sphere plan (TEMX_DUMP_CROW=<file> in the
+environment) -- the engine's own class table, for a byte comparison between two builds (TEMX_LIB):
+TEMX_DUMP_CROW=out.bin dump_crow.py ne [f32]     (f32: the plan for fp32 fields, TEMX_LAT_TOL_F32)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pytemdiags_amd import engine, synth
 lat, lon = synth.cubed_sphere_gll(int(sys.argv[1]))
 e = np.arange(-90, 91, 1.0)
-plan = engine.Plan(lat, (e[1:] + e[:-1]) / 2, 50)
+plan = engine.Plan(lat, (e[1:] + e[:-1]) / 2, 50, fp32_fields=len(sys.argv) > 2 and sys.argv[2] == "f32")
 print("plan built; single_sweep", plan.single_sweep)
