@@ -43,7 +43,8 @@ enum {
   TEMX_ESTATE = -5,   /* call order violated (plan not finalised, TEM levels not set, ...) */
   TEMX_EUNSUPPORTED = -6,
   TEMX_EINTERNAL = -7 /* a C++ exception inside the library (reported, never propagated across this ABI);
-                         host allocation failures come back as TEMX_ENOMEM */
+                         host allocation failures come back as TEMX_ENOMEM.  From temx_status: a kernel reported
+                         an internal failure (see TEMX_OPT_OS_SYNC) */
 };
 
 enum {
@@ -85,8 +86,13 @@ enum {
                                       pseudo-inverse */
   TEMX_OPT_MIN_COVERAGE = 9,       /* missing-value mode: outputs whose coverage is below value / 1000 are NaN
                                       (0..1000, default 500; 0 disables the coverage mask) */
-  TEMX_OPT_MISSING_WEIGHT = 10     /* missing-value mode: tau = 10^-value, the weight of a missing point as an
+  TEMX_OPT_MISSING_WEIGHT = 10,    /* missing-value mode: tau = 10^-value, the weight of a missing point as an
                                       observation of 0 (4..14, default 10) */
+  TEMX_OPT_OS_SYNC = 11            /* single sweep of fp64 fields, how the four waves of a workgroup hand the class sums
+                                      of a class-group over: 0 through counters in LDS, no wave waits for the slowest
+                                      (default), 1 through two workgroup barriers (A/B; env: TEMX_OS_SYNC=barrier).
+                                      The results are the same bit for bit.  A hand-over that times out (it never
+                                      should) makes temx_status return TEMX_EINTERNAL */
 };
 /* Missing-value mode (TEMX_OPT_MISSING = 1).
  *   Missing point: a value that is not finite (NaN, +-Inf).  TEM pipeline: one common mask per (column, level, time),

@@ -24,6 +24,7 @@ MAT_COVERAGE = 8
 OPT_FORM, OPT_OS_MAP, OPT_OP_MAP, OPT_OS_SUBSAMPLE, OPT_TRACER_ONE_PASS, OPT_SINGLE_SWEEP_MIN_GROUPS, OPT_OS_CONTRACT = 1, 2, 3, 4, 5, 6, 7
 # missing-value mode (include/temx.h): 0 raise / 1 mask, coverage threshold in per mille, tau = 10^-value
 OPT_MISSING, OPT_MIN_COVERAGE, OPT_MISSING_WEIGHT = 8, 9, 10
+OPT_OS_SYNC = 11          # single sweep of fp64 fields: 0 hand-over by LDS flags (default), 1 by workgroup barriers (A/B)
 MISSING_MODES = {"raise": 0, "mask": 1}
 FORM_AUTO, FORM_TWO_PASS, FORM_CLASS_SUMS, FORM_SINGLE_SWEEP, FORM_NO_SINGLE_SWEEP = -1, 0, 1, 2, 3
 FORM_MASKED = 4

@@ -687,13 +687,37 @@ __device__ __forceinline__ void row_touch(T& a) {      // orders the uses of a b
 //     (lane = class slot x column, the MFMA B layout) for the reference, the shifted sums and the projection,
 //     which is deferred over the next four batches as in sweep_os_kernel<DEFER = 1>.
 // The Y blocks of a group are the same for the four waves: one shared copy, double buffered.
+//
+// SYNC = 1: the hand-over without barriers.  Two counters in LDS count arrivals and are never reset: `ready` gets
+// one ds_add per wave that has written its class's values and its Y quarter of a group (after s_waitcnt lgkmcnt(0):
+// the LDS operations of a wave retire in order), `done` one per wave that has read a group's exchange area into
+// registers.  With n groups handed over by a wave so far,
+//   * the producer (reading role, end of group n) waits for done >= 4 n before it writes: every wave has read group
+//     n - 1 out of the single exchange area.  A wave flushes what is left of the projection of group n - 2 before it
+//     reads group n - 1, so by then nobody reads the Y buffer of group n - 2 either, which is the one group n takes:
+//     two Y buffers are enough.  Then it goes straight on to the next step, whose first act is the next issue;
+//   * the consumer (tile role) runs after the first issue of the following group, or after the loop for the last
+//     group of a work cut: it waits for ready >= 4 (n + 1), reads the exchange area, runs the reference MFMAs, forms
+//     dS / dP and sets left = NCH, as the barrier form does at the group end.
+// Same sums, same MFMAs, same order per accumulator: the results equal the barrier form's bit for bit.
+// No wave can wait for ever.  A wave waits for `ready` of group n only after it has arrived for group n itself, and
+// for `done` of group n - 1 only after it has read group n - 1 itself; the slowest wave (fewest groups handed over,
+// say m) is therefore never kept by a faster one: the `done` it may wait for needs every wave to read group m - 1,
+// which needs `ready` of m - 1, and all four have arrived there since all are at m or beyond; the `ready` of m it
+// waits for next needs the others to pass the same `done`.  Both waits look at most HANDOFF_LOOKS times (an s_sleep
+// each, several orders of magnitude beyond a group's few microseconds); a wave that gives up stops waiting, runs
+// to its end and ORs a code into hstat[0], which temx_status reports as TEMX_EINTERNAL.
 // ------------------------------------------------------------------------------------------------
-template <typename T, int TBS, int TBX, int NBR, int PD, int KIND = 0>
+constexpr int HANDOFF_LOOKS = 1 << 22;
+__device__ __forceinline__ uint32_t handoff_look(const uint32_t* ctr) {      // a real LDS read each time
+  return __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+template <typename T, int TBS, int TBX, int NBR, int PD, int KIND = 0, int SYNC = 0>
 __global__ void __launch_bounds__(256, 1)
 sweep_osr_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __restrict__ ycx,
                  const int4* __restrict__ crow, const int2* __restrict__ csplit,
                  const double* __restrict__ colscale, const double* __restrict__ rho, int K4,
-                 double* __restrict__ px, double* __restrict__ pp, int nsplit, int ndt) {
+                 double* __restrict__ px, double* __restrict__ pp, int nsplit, int ndt, int* __restrict__ hstat) {
   using KD = OsKind<KIND>;
   constexpr int NF = KD::NF, NFX = KD::NFX, NP = KD::NP;
   constexpr int NBX = 2 * TBX;
@@ -707,7 +731,7 @@ sweep_osr_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
   static_assert(YJ <= 2, "Y quarter per thread");
   static_assert((PD - 1) * CLS_MB * KD::NF + (CLS_MB - 1) * KD::NF + 2 <= 63, "the ring is counted in vmcnt (6 bits)");
   // [2][YE] Y blocks | [16] member counts | [4 waves][NF][2 NBR][64] reference operands |
-  // [4 waves][NP - NPR][2 TBS][64] product accumulators | [NV][4 classes][64 columns] exchange
+  // [4 waves][NP - NPR][2 TBS][64] product accumulators | [NV][4 classes][64 columns] exchange | SYNC = 1: ready, done
   extern __shared__ double lds[];
   int split, dq;
   if (!wg_work((ndt + 3) / 4, nsplit, split, dq)) return;
@@ -734,7 +758,12 @@ sweep_osr_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
   double* ex = lds + 2 * YE + 16 + 4 * (NF * 2 * NBR * 64) + 4 * (NPL * 2 * TBS * 64);
   double* exw = ex + wave * 64 + lane;                   // [v][my class][my column]
   const double* exr = ex + g * 64 + wave * 16 + c;       // [v][class g][column of my d-tile]
+  uint32_t* hctr = reinterpret_cast<uint32_t*>(ex + NV * 256);   // [0] ready, [1] done
   const double sth = (KD::TF >= 0 && colscale != nullptr) ? colscale[colr] : 1.0;
+  if constexpr (SYNC != 0) {
+    if (tid < 2) hctr[tid] = 0u;
+    __syncthreads();
+  }
 #pragma unroll
   for (int i = 0; i < NPL * 2 * TBS; ++i) apl[i * 64] = 0.0;
   double apr[NPR > 0 ? NPR : 1][2 * TBS];
@@ -827,14 +856,100 @@ sweep_osr_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
     cntN = cnt;
     cnt = 0.0;
   };
+  // ---- tile role: class slot g, column c of d-tile `wave`; yw = the Y blocks of the group
+  auto tile_role = [&](const double* yw) __attribute__((always_inline)) {
+    double m2[2][NF], c2[2][NP];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      m2[0][f] = exr[f * 256];
+      m2[1][f] = exr[(NF + NP + f) * 256];
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      c2[0][k] = exr[(NF + k) * 256];
+      c2[1][k] = exr[(2 * NF + NP + k) * 256];
+    }
+    const double nN = cn[g], nS = cn[4 + g];
+    // reference at the class latitudes: E = even part, O = odd part; r_N = E + O, r_S = E - O
+    double E[NF], O[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) E[f] = O[f] = 0.0;
+#pragma unroll
+    for (int tb = 0; tb < ((TEMX_OS_SKIP & 2) ? 0 : 2 * NBR); ++tb) {
+      const int blk = tb < NBR ? tb : TBX + (tb - NBR);
+      const double ya = yw[blk * 16 + aoff_r];
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        if (tb < NBR)
+          E[f] = TEMX_MFMA4(ya, cb[(f * 2 * NBR + tb) * 64], E[f]);
+        else
+          O[f] = TEMX_MFMA4(ya, cb[(f * 2 * NBR + tb) * 64], O[f]);
+      }
+    }
+    if constexpr (SYNC != 0) {                // the exchange area is in registers: hand it back
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (lane == 0) __hip_atomic_fetch_add(&hctr[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      m2[0][f] -= E[f] + O[f];              // side mean minus the reference
+      m2[1][f] -= E[f] - O[f];
+    }
+#pragma unroll
+    for (int f = 0; f < NFX; ++f) {
+      const double SNf = nN * m2[0][f], SSf = nS * m2[1][f];
+      dS[f][0] = SNf + SSf;
+      dS[f][1] = SNf - SSf;
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const double PNk = c2[0][k] + nN * m2[0][KD::pa(k)] * m2[0][KD::pb(k)];
+      const double PSk = c2[1][k] + nS * m2[1][KD::pa(k)] * m2[1][KD::pb(k)];
+      dP[k][0] = PNk + PSk;
+      dP[k][1] = PNk - PSk;
+    }
+    yprev = yw;
+    left = NCH;
+  };
+  // ---- SYNC = 1: the hand-over state of this wave (all wave-uniform)
+  uint32_t hgen = 0;                          // groups this wave has handed over
+  bool hpend = false;                         // the last of them has not been taken over yet
+  int hfail = 0;                              // 1: `ready` never came, 2: `done` never came (the wave waits no more)
+  const double* ypend = ybase;
+  auto handoff_wait = [&](const uint32_t* ctr, uint32_t seen, uint32_t need, int code) __attribute__((always_inline)) {
+    seen = (uint32_t)__builtin_amdgcn_readfirstlane((int)seen);
+    if (seen >= need || hfail != 0) return;   // (normally true at the first look)
+#pragma unroll 1
+    for (int n = 0; n < HANDOFF_LOOKS; ++n) {
+      __builtin_amdgcn_s_sleep(1);
+      seen = (uint32_t)__builtin_amdgcn_readfirstlane((int)handoff_look(ctr));
+      if (seen >= need) return;
+    }
+    hfail = code;
+  };
   int4 rn;
   auto step = [&](auto posc, int b) __attribute__((always_inline)) {
     constexpr int POS = decltype(posc)::value % NCH;
     constexpr int P = decltype(posc)::value % PD;
+    uint32_t seen = 0;
+    if constexpr (SYNC != 0) {
+      if (hpend) seen = handoff_look(&hctr[0]);   // (answered while the batch is being issued)
+    }
     {                                         // (past b1: the next cut's rows or the table's padding, never used)
       const int4 r1 = rn;
       rn = crow[(int64_t)(b + PD) * 4 + wave];
       issue(std::integral_constant<int, (P + PD - 1) % PD>{}, r1);
+    }
+    if constexpr (SYNC != 0) {
+      if (hpend) {                            // take over the group that ended with the previous step
+        if (left > 0)                         // (it followed a group shorter than NCH steps: dS / dP are single)
+          static_for<NCH>([&](auto cc) __attribute__((always_inline)) {
+            if (((decltype(cc)::value - POS) & (NCH - 1)) < left) pending_chunk(cc);
+          });
+        handoff_wait(&hctr[0], seen, 4u * hgen, 1);
+        tile_role(ypend);
+        hpend = false;
+      }
     }
     if (left > 0) {                           // the loads of the next batch are in flight meanwhile
       if (!(TEMX_OS_SKIP & 1)) pending_chunk(std::integral_constant<int, POS>{});
@@ -875,10 +990,15 @@ sweep_osr_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
       prev_south = false;
       if (north_open) park_north();           // the group has no southern batch: the open side is the northern one
       north_open = false;
-      if (left > 0)                           // (a group shorter than NCH steps: what is left of the previous projection)
-        static_for<NCH>([&](auto cc) __attribute__((always_inline)) {
-          if (((decltype(cc)::value - POS - 1) & (NCH - 1)) < left) pending_chunk(cc);
-        });
+      uint32_t seen_done = 0;
+      if constexpr (SYNC == 0) {
+        if (left > 0)                         // (a group shorter than NCH steps: what is left of the previous projection)
+          static_for<NCH>([&](auto cc) __attribute__((always_inline)) {
+            if (((decltype(cc)::value - POS - 1) & (NCH - 1)) < left) pending_chunk(cc);
+          });
+      } else {
+        seen_done = handoff_look(&hctr[1]);   // (the taker-over of the next group flushes what is left)
+      }
       // ---- reading role: side means (theta = T x the column scale) and central co-moments of my class
       const double rnN = cntN > 0.0 ? temx_rcp_count(cntN) : 0.0, rnS = cnt > 0.0 ? temx_rcp_count(cnt) : 0.0;
       double val[NV];
@@ -895,7 +1015,11 @@ sweep_osr_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
         val[2 * NF + NP + k] = (q[k] - s[KD::pa(k)] * s[KD::pb(k)] * rnS) * sc;
       }
       // every wave is done with the exchange area of the previous group (LDS reads retired, loads stay in flight)
-      if (!(TEMX_OS_SKIP & 8)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if constexpr (SYNC == 0) {
+        if (!(TEMX_OS_SKIP & 8)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      } else {
+        handoff_wait(&hctr[1], seen_done, 4u * hgen, 2);
+      }
       ycur ^= 1;
       double* yw = ybase + ycur * YE;
 #pragma unroll
@@ -907,58 +1031,18 @@ sweep_osr_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
 #pragma unroll
       for (int j = 0; j < YJ; ++j)
         if (tid + 256 * j < YE) yw[tid + 256 * j] = ys[j];
-      if (!(TEMX_OS_SKIP & 8)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if constexpr (SYNC == 0) {
+        if (!(TEMX_OS_SKIP & 8)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      } else {                                // arrived: no barrier, the next step issues the next batch at once
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (lane == 0) __hip_atomic_fetch_add(&hctr[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        ++hgen;
+        hpend = true;
+        ypend = yw;
+      }
       ++grp;
       load_ys(grp);
-      // ---- tile role: class slot g, column c of d-tile `wave`
-      double m2[2][NF], c2[2][NP];
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        m2[0][f] = exr[f * 256];
-        m2[1][f] = exr[(NF + NP + f) * 256];
-      }
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        c2[0][k] = exr[(NF + k) * 256];
-        c2[1][k] = exr[(2 * NF + NP + k) * 256];
-      }
-      const double nN = cn[g], nS = cn[4 + g];
-      // reference at the class latitudes: E = even part, O = odd part; r_N = E + O, r_S = E - O
-      double E[NF], O[NF];
-#pragma unroll
-      for (int f = 0; f < NF; ++f) E[f] = O[f] = 0.0;
-#pragma unroll
-      for (int tb = 0; tb < ((TEMX_OS_SKIP & 2) ? 0 : 2 * NBR); ++tb) {
-        const int blk = tb < NBR ? tb : TBX + (tb - NBR);
-        const double ya = yw[blk * 16 + aoff_r];
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          if (tb < NBR)
-            E[f] = TEMX_MFMA4(ya, cb[(f * 2 * NBR + tb) * 64], E[f]);
-          else
-            O[f] = TEMX_MFMA4(ya, cb[(f * 2 * NBR + tb) * 64], O[f]);
-        }
-      }
-#pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        m2[0][f] -= E[f] + O[f];              // side mean minus the reference
-        m2[1][f] -= E[f] - O[f];
-      }
-#pragma unroll
-      for (int f = 0; f < NFX; ++f) {
-        const double SNf = nN * m2[0][f], SSf = nS * m2[1][f];
-        dS[f][0] = SNf + SSf;
-        dS[f][1] = SNf - SSf;
-      }
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        const double PNk = c2[0][k] + nN * m2[0][KD::pa(k)] * m2[0][KD::pb(k)];
-        const double PSk = c2[1][k] + nS * m2[1][KD::pa(k)] * m2[1][KD::pb(k)];
-        dP[k][0] = PNk + PSk;
-        dP[k][1] = PNk - PSk;
-      }
-      yprev = yw;
-      left = NCH;
+      if constexpr (SYNC == 0) tile_role(yw);
 #pragma unroll
       for (int f = 0; f < NF; ++f) s[f] = sN[f] = 0.0;
 #pragma unroll
@@ -985,6 +1069,19 @@ sweep_osr_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
     // the batches issued past b1 and the last Y prefetch are still landing in registers the compiler believes
     // free from here on: drain them before anything else is written there
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  if constexpr (SYNC != 0) {
+    if (hpend) {                              // the last group of the work cut
+      if (left > 0) {
+        const int first = (b1 - b0) & (NCH - 1);
+        static_for<NCH>([&](auto cc) __attribute__((always_inline)) {
+          if (((decltype(cc)::value - first) & (NCH - 1)) < left) pending_chunk(cc);
+        });
+      }
+      handoff_wait(&hctr[0], handoff_look(&hctr[0]), 4u * hgen, 1);
+      tile_role(ypend);
+    }
+    if (hfail != 0 && lane == 0) atomicOr(hstat, hfail);
   }
   if (left > 0) {
     const int first = (b1 - b0) & (NCH - 1);

@@ -156,6 +156,8 @@ struct temx_plan {
   OscMats osc{};
   bool osc_lds = false;                // TEMX_OPT_OS_CONTRACT = 1 / TEMX_OS_CONTRACT=lds: the round-3 LDS form (A/B)
   int opt_os_contract = -1;
+  bool os_barrier = false;             // TEMX_OPT_OS_SYNC = 1 / TEMX_OS_SYNC=barrier: the single sweep of fp64 fields hands its
+  int opt_os_sync = -1;                // class sums over through two workgroup barriers per group instead of LDS flags (A/B)
   int os_keep = 32;                    // class-groups of the reference subsample (TEMX_OPT_OS_SUBSAMPLE): 128 latitudes for 16 coefficients per column
   // what the tail of the pipeline (solve, contraction, scan, epilogue) currently describes: the snapshots
   // [tt0, tt0 + tnt) of the run, tD = nlev * tnt columns.  The whole run unless a time-sliced tail ran last.
@@ -1808,14 +1810,17 @@ static int launch_sweep_os_t(temx_plan* pl, const FieldPtrs<4>& fp, bool sub, co
                          static_cast<const int*>(pl->side_gfirst[si][0].p), static_cast<const int*>(pl->side_gfirst[si][1].p), \
                          cuts, pl->colscale.d(), rho, pl->KR, px, pp, sp.nsplit, sp.ndt);                           \
     } else {                                                                                                        \
-      auto kern = sweep_osr_kernel<double, TBSv, TBXv, NBR, 2, KIND>;                                               \
-      const size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +                      \
-                          (size_t)4 * (KD::NP - KD::NPR) * 2 * TBSv * 64 + (size_t)2 * (KD::NF + KD::NP) * 256) * 8; \
-      static std::atomic<uint64_t> attr_set{0};                                                                     \
-      if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) return rc_; \
+      /* Y blocks x 2 | counts | reference operands | product accumulators | exchange | the flag form's two counters */ \
+      constexpr size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +                  \
+                              (size_t)4 * (KD::NP - KD::NPR) * 2 * TBSv * 64 + (size_t)2 * (KD::NF + KD::NP) * 256 + 2) * 8; \
+      static_assert(lds <= 163840, "the single sweep's workgroup fits the LDS of a compute unit");                 \
+      auto kern = pl->os_barrier ? sweep_osr_kernel<double, TBSv, TBXv, NBR, 2, KIND, 0>                            \
+                                 : sweep_osr_kernel<double, TBSv, TBXv, NBR, 2, KIND, 1>;                           \
+      static std::atomic<uint64_t> attr_set[2] = {{0}, {0}};                                                        \
+      if (int rc_ = lds_attr_once(attr_set[pl->os_barrier ? 0 : 1], pl->device, reinterpret_cast<const void*>(kern), (int)lds)) return rc_; \
       hipLaunchKernelGGL(kern, grid, block, lds, st, fp, pl->D, pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(),   \
                          static_cast<const int4*>(sub ? pl->crow_s.p : pl->crow.p), cuts, pl->colscale.d(), rho,    \
-                         pl->KR, px, pp, sp.nsplit, sp.ndt);                                                        \
+                         pl->KR, px, pp, sp.nsplit, sp.ndt, static_cast<int*>(pl->flag.p) + 1);                     \
     }                                                                                                               \
   } while (0)
   if (pl->TBS == 7 && pl->TBX == 13) TEMX_LOS(7, 13);
@@ -2381,8 +2386,8 @@ int temx_plan_create(temx_plan** out, int device, int64_t ncol, int L, int M,
   std::vector<double> norm((size_t)std::max(64, pl->K4), 0.0);
   for (int l = 0; l < pl->K; ++l) norm[l] = std::sqrt((2.0 * l + 1.0) / (4.0 * M_PI));
   if ((rc = upload(pl->norm, norm.data(), norm.size() * 8))) return bail(rc);
-  int zero = 0;
-  if ((rc = upload(pl->flag, &zero, sizeof(int)))) return bail(rc);
+  const int zero[2] = {0, 0};          // [0] non-finite input seen, [1] the single sweep's hand-over status
+  if ((rc = upload(pl->flag, zero, sizeof(zero)))) return bail(rc);
 
   if ((rc = pl->Y0.ensure((size_t)ncol * pl->K * 8))) return bail(rc);
   // one extra chunk of blocks: the sweeps prefetch A operands one group / step ahead
@@ -2837,6 +2842,10 @@ static bool tile_map(int opt, const char* env) {
   if (const char* e = getenv(env)) return !strcmp(e, "tile");
   return opt == 1;
 }
+static bool os_barrier_wanted(const temx_plan* pl) {
+  if (const char* e = getenv("TEMX_OS_SYNC")) return !strcmp(e, "barrier");
+  return pl->opt_os_sync == 1;
+}
 static bool tracer_one_pass_wanted(const temx_plan* pl) {
   if (const char* e = getenv("TEMX_TRACER_ONE_PASS")) return e[0] == '1';
   return pl->opt_tracer_one_pass == 1;
@@ -2874,6 +2883,10 @@ int temx_plan_configure(temx_plan* pl, int option, int value) try {
       if (value < 4 || value > 14) return fail(TEMX_EINVAL, "TEMX_OPT_MISSING_WEIGHT: tau = 10^-value, value in 4..14, got %d", value);
       pl->opt_miss_w = value;
       break;
+    case TEMX_OPT_OS_SYNC:
+      if (value != 0 && value != 1) return fail(TEMX_EINVAL, "TEMX_OPT_OS_SYNC: 0 (flags) or 1 (barriers), got %d", value);
+      pl->opt_os_sync = value;
+      break;
     default: return fail(TEMX_EINVAL, "unknown option %d", option);
   }
   pl->tem = false;                // the choice is made in temx_plan_set_tem: call it (again)
@@ -2895,6 +2908,7 @@ int temx_plan_option(const temx_plan* pl, int option) try {
     case TEMX_OPT_MISSING: return pl->opt_missing;
     case TEMX_OPT_MIN_COVERAGE: return pl->opt_min_cov;
     case TEMX_OPT_MISSING_WEIGHT: return pl->opt_miss_w;
+    case TEMX_OPT_OS_SYNC: return os_barrier_wanted(pl) ? 1 : 0;
     default: return -1;
   }
 } TEMX_CATCH
@@ -2920,6 +2934,7 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
     pl->osc_lds = e ? !strcmp(e, "lds") : pl->opt_os_contract == 1;
   }
   pl->op_tile = tile_map(pl->opt_op_map, "TEMX_OP_MAP");
+  pl->os_barrier = os_barrier_wanted(pl);
   pl->nlev = nlev;
   pl->nt = nt;
   pl->D = (int64_t)nlev * nt;
@@ -3963,13 +3978,17 @@ int temx_status(temx_plan* pl, int* nonfinite, void* stream) try {
   if (!pl || !nonfinite) return fail(TEMX_EINVAL, "null argument");
   HIPCHK(hipSetDevice(pl->device));
   HIPCHK(hipStreamSynchronize(S_(stream)));
-  int f = 0;
-  HIPCHK(hipMemcpy(&f, pl->flag.p, sizeof(int), hipMemcpyDeviceToHost));
+  int fw[2] = {0, 0};
+  HIPCHK(hipMemcpy(fw, pl->flag.p, sizeof(fw), hipMemcpyDeviceToHost));
+  const int f = fw[0];
   *nonfinite = miss_mode(pl) ? 0 : f;     // missing-value mode: non-finite input is data, not an error
-  if (f) {
-    int zero = 0;
-    HIPCHK(hipMemcpy(pl->flag.p, &zero, sizeof(int), hipMemcpyHostToDevice));
+  if (f || fw[1]) {
+    const int zero[2] = {0, 0};
+    HIPCHK(hipMemcpy(pl->flag.p, zero, sizeof(zero), hipMemcpyHostToDevice));
   }
+  if (fw[1])   // (kernels_op2.hpp, sweep_osr_kernel<SYNC = 1>: a wave gave up waiting; the results of that run are not valid)
+    return fail(TEMX_EINTERNAL, "single sweep: the hand-over of the class sums between the waves of a workgroup timed out "
+                "(code %d); results of the runs since the last temx_status are invalid. TEMX_OS_SYNC=barrier selects the barrier form", fw[1]);
   return TEMX_OK;
 } TEMX_CATCH
 

@@ -78,13 +78,15 @@ class Plan:
 
     def configure(self, form=None, os_map=None, op_map=None, os_subsample=None, tracer_one_pass=None,
                   single_sweep_min_groups=None, os_contract=None, missing=None, min_coverage=None,
-                  missing_weight=None):
+                  missing_weight=None, os_sync=None):
         """Path selection (temx_plan_configure); ``set_tem`` must follow.  ``form``: a key of ``_lib.FORMS``
         ("auto", "two-pass", "class-sums", "single-sweep", "no-single-sweep"); ``os_map`` / ``op_map``:
         "row" or "tile" (lane map of the loads of the single sweep / of sweep 1 of the class-sum form).
         ``missing``: "raise" (default) or "mask" -- non-finite values are missing points of a masked fit
         (include/temx.h, missing-value mode); ``min_coverage`` in [0, 1] (outputs whose coverage is below it are
-        NaN, 0 disables; default 0.5); ``missing_weight`` tau, a power of ten in [1e-14, 1e-4] (default 1e-10)."""
+        NaN, 0 disables; default 0.5); ``missing_weight`` tau, a power of ten in [1e-14, 1e-4] (default 1e-10).
+        ``os_sync``: "flags" (default) or "barrier" -- how the waves of the single sweep of fp64 fields hand a
+        class-group's sums over (same bits; A/B)."""
         def put(opt, val):
             check(self.lib.temx_plan_configure(self._h, opt, int(val)))
         if missing is not None:
@@ -115,6 +117,8 @@ class Plan:
             put(_lib.OPT_SINGLE_SWEEP_MIN_GROUPS, single_sweep_min_groups)
         if os_contract is not None:     # "mfma" (default) or "lds" (the round-3 form, A/B)
             put(_lib.OPT_OS_CONTRACT, {"mfma": 0, "lds": 1}[os_contract] if isinstance(os_contract, str) else os_contract)
+        if os_sync is not None:
+            put(_lib.OPT_OS_SYNC, {"flags": 0, "barrier": 1}[os_sync] if isinstance(os_sync, str) else os_sync)
         self.nlev = self.nt = self.D = None
 
     def option(self, opt):

@@ -272,6 +272,7 @@ int run(int64_t N, int64_t D, int reps, const char* only) {
   int bad = 0;
 
   struct Variant { std::string name; int nsplit; std::function<void(double*)> launch; };
+  static int* hstat = nullptr;                 // the flag form's status word (0 unless a wave gave up waiting)
   double *px = nullptr, *pp = nullptr; size_t os_px_n = 0, os_pp_n = 0, os_nsplit = 0;   // outputs of the single-sweep variants
   auto os_fits = [&](int nsplit) {              // a single-sweep variant writes nsplit slabs of px and of pp
     if ((size_t)nsplit <= os_nsplit) return;
@@ -335,18 +336,22 @@ int run(int64_t N, int64_t D, int reps, const char* only) {
         hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(256), ldsb, 0, fp, D, K, KX, ycx_, reinterpret_cast<const int4*>(d_crow), cuts,
                            d_cs, rho_, K4r, px_, pp_, sp.nsplit, sp.ndt); }});
     };
-    auto add_osr = [&](auto nbrc, auto pdc) {
-      constexpr int NBR = decltype(nbrc)::value, PD = decltype(pdc)::value;
+    if (!hstat) { CHK(hipMalloc(&hstat, sizeof(int))); CHK(hipMemset(hstat, 0, sizeof(int))); }
+    auto add_osr = [&](auto nbrc, auto pdc, auto syc) {
+      constexpr int NBR = decltype(nbrc)::value, PD = decltype(pdc)::value, SY = decltype(syc)::value;
       Split sp = choose_split(D, cunits, getenv("LAB_SLOTS") ? atoi(getenv("LAB_SLOTS")) : 256, 4, 8);
       int2* cuts = reinterpret_cast<int2*>(to_dev(group_cuts(gb0, sp.nsplit)));
       os_fits(sp.nsplit);
-      const size_t ldsb = ((size_t)2 * 2 * TBX * 16 + 16 + (size_t)4 * 4 * 2 * NBR * 64 + (size_t)4 * 3 * 2 * TBS * 64 + (size_t)14 * 256) * 8;
-      auto kern = sweep_osr_kernel<T, TBS, TBX, NBR, PD, 0>;
+      const size_t ldsb = ((size_t)2 * 2 * TBX * 16 + 16 + (size_t)4 * 4 * 2 * NBR * 64 + (size_t)4 * 3 * 2 * TBS * 64 + (size_t)14 * 256 + (SY ? 2 : 0)) * 8;
+      static_assert(((size_t)2 * 2 * TBX * 16 + 16 + (size_t)4 * 4 * 2 * NBR * 64 + (size_t)4 * 3 * 2 * TBS * 64 + (size_t)14 * 256 + 2) * 8 <= 163840, "LDS of a workgroup");
+      auto kern = sweep_osr_kernel<T, TBS, TBX, NBR, PD, 0, SY>;
       CHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
       double *ycx_ = ycx, *rho_ = rho, *px_ = px, *pp_ = pp;
-      vars.push_back({"osr   ONE sweep, loads of 1 row x 64 columns, exchange at the group's end, PD=" + std::to_string(PD), 0, [=](double*) {
+      int* hstat_ = hstat;
+      vars.push_back({"osr   ONE sweep, loads of 1 row x 64 columns, exchange at the group's end, PD=" + std::to_string(PD) +
+                      (SY ? ", flags" : ", barriers"), 0, [=](double*) {
         hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(256), ldsb, 0, fp, D, K, KX, ycx_, reinterpret_cast<const int4*>(d_crow), cuts,
-                           d_cs, rho_, K4r, px_, pp_, sp.nsplit, sp.ndt); }});
+                           d_cs, rho_, K4r, px_, pp_, sp.nsplit, sp.ndt, hstat_); }});
     };
     static int *d_crowN = nullptr, *d_crowS = nullptr, *d_gfN = nullptr, *d_gfS = nullptr;
     if (!d_crowN) {
@@ -370,10 +375,19 @@ int run(int64_t N, int64_t D, int reps, const char* only) {
     };
     add_os2(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
     add_os2(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{});
-    add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
-    add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{});
-    add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});     // (vmcnt counts to 63: 3 x 16 + 12 loads)
     using N0 = std::integral_constant<int, 0>; using N1 = std::integral_constant<int, 1>;
+    // LAB_AB_ROUNDS=n: the barrier form and the flag form n times in turn (the A/B of the hand-over), nothing else of osr
+    const int ab_rounds = getenv("LAB_AB_ROUNDS") ? atoi(getenv("LAB_AB_ROUNDS")) : 0;
+    for (int r = 0; r < ab_rounds; ++r) {
+      add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, N0{});
+      add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, N1{});
+    }
+    if (ab_rounds == 0) {
+      add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, N0{});
+      add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, N1{});
+      add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{}, N0{});
+      add_osr(std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{}, N0{});     // (vmcnt counts to 63: 3 x 16 + 12 loads)
+    }
     add_os(std::integral_constant<int, 2>{}, std::integral_constant<int, sizeof(T) == 8 ? 2 : 4>{}, N0{});
     add_os(std::integral_constant<int, 2>{}, std::integral_constant<int, sizeof(T) == 8 ? 2 : 4>{}, N1{});
 #ifndef LAB_OS_FEW
@@ -463,6 +477,11 @@ int run(int64_t N, int64_t D, int reps, const char* only) {
       for (size_t i = 0; i < h.size(); ++i) { dm_ = std::max(dm_, std::fabs(h[i] - os_ref[i])); rm_ = std::max(rm_, std::fabs(os_ref[i])); }
       printf("    outputs vs the first single-sweep variant: max |diff| / max |ref| = %.2e (max |ref| %.3e)\n", dm_ / rm_, rm_);
       if (!(dm_ <= 1e-11 * rm_)) ++bad;
+      if (hstat) {
+        int hs = 0;
+        CHK(hipMemcpy(&hs, hstat, sizeof(int), hipMemcpyDeviceToHost));
+        if (hs) { printf("    HAND-OVER STATUS %d: a wave gave up waiting for a counter\n", hs); ++bad; CHK(hipMemset(hstat, 0, sizeof(int))); }
+      }
       CHK(hipMemset(px, 0, os_px_n * 8)); CHK(hipMemset(pp, 0, os_pp_n * 8));
     }
 #ifdef LAB_OFFSETS
