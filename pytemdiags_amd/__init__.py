@@ -9,6 +9,7 @@ CPU fallback: the engine raises if the extension is not built or no GPU is visib
 from .sph_zonal_mean import sph_zonal_averager
 from .tem_diagnostics import TEMDiagnostics
 from .containers import LabeledArray
+from .vertical import interp_to_pressure
 
-__all__ = ["TEMDiagnostics", "sph_zonal_averager", "LabeledArray"]
+__all__ = ["TEMDiagnostics", "sph_zonal_averager", "LabeledArray", "interp_to_pressure"]
 __version__ = "0.1"

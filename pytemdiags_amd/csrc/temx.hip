@@ -1,6 +1,7 @@
 // temx.hip -- host side of libtemx.so: plan, workspace, launch logic and the C ABI of
 // include/temx.h.  gfx950 only.  Build: see csrc/Makefile (hipcc --offload-arch=gfx950).
 #include "../../include/temx.h"
+#include "../../include/temx_vert.h"
 
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <mutex>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -26,6 +28,7 @@
 #include "kernels_osc.hpp"
 #include "side_tables.hpp"
 #include "kernels_miss.hpp"
+#include "kernels_vert.hpp"
 
 using namespace temx;
 
@@ -2222,6 +2225,101 @@ static int launch_miss_native(temx_plan* pl, const void* A, int dtype, int64_t D
   return TEMX_OK;
 }
 
+// ---- vertical interpolation: launchers (kernels_vert.hpp, include/temx_vert.h) -----------------------------------
+// The tables of a call (hyam, hybm, pt, xt) live in device buffers that are never written again once uploaded, so
+// calls on any stream may share them: a call with a set seen before touches no allocator.
+struct VertTables {
+  int device;
+  std::vector<double> host;
+  double* dev;
+};
+static std::mutex g_vert_mu;
+static std::vector<VertTables> g_vert_tabs;
+constexpr size_t VERT_TABLE_SETS = 16;
+
+static int vert_tables(int device, const std::vector<double>& host, const double** dev) {
+  std::lock_guard<std::mutex> lk(g_vert_mu);
+  for (const VertTables& e : g_vert_tabs)
+    if (e.device == device && e.host == host) {
+      *dev = e.dev;
+      return TEMX_OK;
+    }
+  if (g_vert_tabs.size() >= VERT_TABLE_SETS) {   // hipFree waits for the kernels that may still read the oldest set
+    (void)hipFree(g_vert_tabs.front().dev);
+    g_vert_tabs.erase(g_vert_tabs.begin());
+  }
+  double* d = nullptr;
+  HIPCHK(hipMalloc(&d, host.size() * sizeof(double)));
+  hipError_t e = hipMemcpy(d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return fail(TEMX_EHIP, "upload of the level tables failed: %s", hipGetErrorString(e));
+  }
+  g_vert_tabs.push_back(VertTables{device, host, d});
+  *dev = d;
+  return TEMX_OK;
+}
+
+// The slab-staged map: how many columns a workgroup takes and how their walks are cut, from an LDS budget of 48 KiB
+// (three workgroups per CU: one loads while another walks).  false: one column does not fit (long rows).
+static bool vert_slab_shape(int nf, int nlev, int64_t nt, int nplev, size_t tsz, size_t psz, VertSlab* sh, size_t* lds) {
+  if (nt > VERT_THREADS / 4) return false;
+  const int colsz = nlev * (int)nt, ocolsz = nplev * (int)nt;
+  sh->in_stride = colsz | 1;
+  sh->out_stride = ocolsz | 1;
+  const size_t percol = (size_t)nf * (sh->in_stride + sh->out_stride) * tsz + (size_t)sh->in_stride * psz;
+  const size_t budget = 48 * 1024 - VERT_THREADS * sizeof(int) - (2 * nf + 1) * 16;
+  int cw = (int)std::min<size_t>(budget / percol, (size_t)(VERT_THREADS / nt));
+  if (cw < 1) return false;
+  sh->cw = cw;
+  const int pairs = cw * (int)nt, brackets = nlev - 1, most = VERT_THREADS / pairs;
+  sh->seg = std::max(4, (brackets + most - 1) / most);
+  sh->nseg = (brackets + sh->seg - 1) / sh->seg;
+  auto r16 = [](size_t b) { return (int)((b + 15) & ~(size_t)15); };
+  sh->in_img = r16((size_t)cw * sh->in_stride * tsz);
+  sh->out_img = r16((size_t)cw * sh->out_stride * tsz);
+  sh->p_img = r16((size_t)cw * sh->in_stride * psz);
+  *lds = VERT_THREADS * sizeof(int) + sh->p_img + (size_t)nf * (sh->in_img + sh->out_img);
+  return true;
+}
+
+template <typename T, int NF, bool HYB>
+static int launch_vert(const VertPtrs<NF>& fp, int nf, int64_t ncol, int nlev, int64_t nt, int nplev, const VertTab& tb,
+                       double p0, const void* P, int p_f32, int logp, int hold, int map, hipStream_t st) {
+  VertSlab sh{};
+  size_t lds = 0;
+  const bool can_slab = vert_slab_shape(nf, nlev, nt, nplev, sizeof(T), HYB ? 0 : (p_f32 ? 4 : 8), &sh, &lds);
+  const bool slab = map == 2 ? can_slab : map == 1 ? false : can_slab && nt * sizeof(T) < 128;
+  if (map == 2 && !can_slab) return fail(TEMX_EUNSUPPORTED, "TEMXV_MAP=slab: one column of this shape does not fit the LDS budget");
+  if (slab) {
+    const int64_t grid = (ncol + sh.cw - 1) / sh.cw;
+    if (grid > 0x7fffffff) return fail(TEMX_EUNSUPPORTED, "too many columns for one launch");
+    hipLaunchKernelGGL((vert_slab_kernel<T, NF, HYB>), dim3((unsigned)grid), dim3(VERT_THREADS), lds, st, fp, nf, ncol, nlev,
+                       (int)nt, nplev, tb, p0, P, p_f32, logp, hold, sh);
+  } else {
+    const int64_t grid = (ncol * nt + VERT_THREADS - 1) / VERT_THREADS;
+    if (grid > 0x7fffffff) return fail(TEMX_EUNSUPPORTED, "too many columns for one launch");
+    hipLaunchKernelGGL((vert_time_kernel<T, NF, HYB>), dim3((unsigned)grid), dim3(VERT_THREADS), 0, st, fp, nf, ncol, nlev,
+                       nt, nplev, tb, p0, P, p_f32, logp, hold);
+  }
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+template <typename T, bool HYB>
+static int launch_vert_nf(int nf, const void* const* src, void* const* dst, int64_t ncol, int nlev, int64_t nt, int nplev,
+                          const VertTab& tb, double p0, const void* P, int p_f32, int logp, int hold, int map,
+                          hipStream_t st) {
+  if (nf <= 4) {
+    VertPtrs<4> fp{};
+    for (int f = 0; f < nf; ++f) fp.src[f] = src[f], fp.dst[f] = dst[f];
+    return launch_vert<T, 4, HYB>(fp, nf, ncol, nlev, nt, nplev, tb, p0, P, p_f32, logp, hold, map, st);
+  }
+  VertPtrs<VERT_NFMAX> fp{};
+  for (int f = 0; f < nf; ++f) fp.src[f] = src[f], fp.dst[f] = dst[f];
+  return launch_vert<T, VERT_NFMAX, HYB>(fp, nf, ncol, nlev, nt, nplev, tb, p0, P, p_f32, logp, hold, map, st);
+}
+
 extern "C" {
 
 int temx_version(void) { return 402; }
@@ -4079,6 +4177,86 @@ int temx_selftest_exception(int kind) try {
   if (kind == 1) throw std::runtime_error("self-test");
   if (kind == 2) throw 42;
   return fail(TEMX_EINVAL, "kind must be 0, 1 or 2");
+} TEMX_CATCH
+
+// ---- vertical interpolation (include/temx_vert.h) ------------------------------------------------
+int temxv_version(void) { return 100; }
+
+int temxv_interp(int device, int nf, const void* const* src_host, void* const* dst_host, int dtype, int64_t ncol,
+                 int nlev, int64_t nt, int nplev, const double* plev_pa_host, int pmode, const double* hyam_host,
+                 const double* hybm_host, double p0_hybrid, const void* ps_or_p, int p_dtype, int method, int edge,
+                 void* stream) try {
+  if (nf < 1 || nf > TEMXV_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", (int)TEMXV_NF_MAX, nf);
+  if (!src_host || !dst_host || !plev_pa_host || !ps_or_p) return fail(TEMX_EINVAL, "null argument");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (p_dtype != TEMX_F64 && p_dtype != TEMX_F32) return fail(TEMX_EINVAL, "p_dtype must be TEMX_F64 or TEMX_F32");
+  if (pmode != TEMXV_P_HYBRID && pmode != TEMXV_P_FIELD) return fail(TEMX_EINVAL, "pmode must be TEMXV_P_HYBRID or TEMXV_P_FIELD");
+  if (method != TEMXV_LOG && method != TEMXV_LINEAR) return fail(TEMX_EINVAL, "method must be TEMXV_LOG or TEMXV_LINEAR");
+  if (edge != TEMXV_EDGE_NAN && edge != TEMXV_EDGE_HOLD) return fail(TEMX_EINVAL, "edge must be TEMXV_EDGE_NAN or TEMXV_EDGE_HOLD");
+  if (ncol < 1 || nt < 1 || nplev < 1 || nlev < 2) return fail(TEMX_EINVAL, "sizes must be positive (nlev at least 2)");
+  if (nlev > (1 << 20) || nplev > (1 << 20) || nt > (int64_t(1) << 31) || ncol > (int64_t(1) << 40))
+    return fail(TEMX_EINVAL, "sizes out of range");
+  const bool hyb = pmode == TEMXV_P_HYBRID;
+  if (hyb && (!hyam_host || !hybm_host)) return fail(TEMX_EINVAL, "hybrid mode needs hyam and hybm");
+  if (hyb && !std::isfinite(p0_hybrid)) return fail(TEMX_EINVAL, "p0_hybrid is not finite");
+  for (int j = 0; j < nplev; ++j)
+    if (!(plev_pa_host[j] > 0.0) || !std::isfinite(plev_pa_host[j]) || (j && !(plev_pa_host[j] > plev_pa_host[j - 1])))
+      return fail(TEMX_EINVAL, "plev must be positive, finite and strictly ascending (entry %d)", j);
+  if (hyb)
+    for (int k = 0; k < nlev; ++k)
+      if (!std::isfinite(hyam_host[k]) || !std::isfinite(hybm_host[k]))
+        return fail(TEMX_EINVAL, "hyam / hybm entry %d is not finite", k);
+  const size_t tsz = dtype == TEMX_F64 ? 8 : 4, psz = p_dtype == TEMX_F64 ? 8 : 4;
+  const size_t in_bytes = (size_t)ncol * nlev * nt * tsz, out_bytes = (size_t)ncol * nplev * nt * tsz;
+  const size_t p_bytes = hyb ? (size_t)ncol * nt * psz : (size_t)ncol * nlev * nt * psz;
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+  };
+  if ((uintptr_t)ps_or_p % psz) return fail(TEMX_EINVAL, "ps_or_p is not aligned to its element size");
+  for (int f = 0; f < nf; ++f) {
+    if (!src_host[f] || !dst_host[f]) return fail(TEMX_EINVAL, "null field pointer (field %d)", f);
+    if ((uintptr_t)src_host[f] % tsz || (uintptr_t)dst_host[f] % tsz)
+      return fail(TEMX_EINVAL, "field %d is not aligned to its element size", f);
+    if (overlap(dst_host[f], out_bytes, ps_or_p, p_bytes)) return fail(TEMX_EINVAL, "dst %d overlaps the pressure input", f);
+    for (int g = 0; g < nf; ++g) {
+      if (src_host[g] && overlap(dst_host[f], out_bytes, src_host[g], in_bytes))
+        return fail(TEMX_EINVAL, "dst %d overlaps src %d", f, g);
+      if (g < f && overlap(dst_host[f], out_bytes, dst_host[g], out_bytes))
+        return fail(TEMX_EINVAL, "dst %d overlaps dst %d", f, g);
+    }
+  }
+  int map = 0;   // 0 by row length, 1 lanes along time, 2 slab staged
+  if (const char* m = getenv("TEMXV_MAP")) map = !strcmp(m, "time") ? 1 : !strcmp(m, "slab") ? 2 : 0;
+
+  // tables: [hyam | hybm] (hybrid) pt xt
+  std::vector<double> host;
+  host.reserve((hyb ? 2 * (size_t)nlev : 0) + 2 * (size_t)nplev + 1);
+  if (hyb) {
+    host.insert(host.end(), hyam_host, hyam_host + nlev);
+    host.insert(host.end(), hybm_host, hybm_host + nlev);
+  }
+  host.insert(host.end(), plev_pa_host, plev_pa_host + nplev);
+  for (int j = 0; j < nplev; ++j) host.push_back(method == TEMXV_LOG ? std::log(plev_pa_host[j]) : plev_pa_host[j]);
+  host.push_back((double)method);
+  HIPCHK(hipSetDevice(device));
+  const double* dev = nullptr;
+  if (int rc = vert_tables(device, host, &dev)) return rc;
+  VertTab tb{};
+  if (hyb) {
+    tb.hyam = dev;
+    tb.hybm = dev + nlev;
+    dev += 2 * (size_t)nlev;
+  }
+  tb.pt = dev;
+  tb.xt = dev + nplev;
+  const int p_f32 = p_dtype == TEMX_F32, logp = method == TEMXV_LOG, hold = edge == TEMXV_EDGE_HOLD;
+  hipStream_t st = S_(stream);
+#define TEMXV_GO(T, H) \
+  launch_vert_nf<T, H>(nf, src_host, dst_host, ncol, nlev, nt, nplev, tb, p0_hybrid, ps_or_p, p_f32, logp, hold, map, st)
+  if (dtype == TEMX_F64) return hyb ? TEMXV_GO(double, true) : TEMXV_GO(double, false);
+  return hyb ? TEMXV_GO(float, true) : TEMXV_GO(float, false);
+#undef TEMXV_GO
 } TEMX_CATCH
 
 }  // extern "C"

@@ -79,11 +79,14 @@ def pressure_levels(nlev: int) -> np.ndarray:
 def analytic_fields(lat_deg, lon_deg, plev_hpa, nt, noise=0.1, seed=0, dtype=np.float64):
     """Return (ua, va, ta, wap), each ``[ncol][nlev][nt]`` C-contiguous.
 
-    Noise is drawn in the order u, v, T, omega from ``default_rng(seed)``.
+    Noise is drawn in the order u, v, T, omega from ``default_rng(seed)``.  ``plev_hpa`` is ``[nlev]``, or
+    ``[ncol][nlev][nt]`` for levels whose pressure differs from point to point (model levels).
     """
     phi = np.deg2rad(np.asarray(lat_deg, dtype=np.float64))[:, None, None]
     lam = np.deg2rad(np.asarray(lon_deg, dtype=np.float64))[:, None, None]
-    p = np.asarray(plev_hpa, dtype=np.float64)[None, :, None]
+    p = np.asarray(plev_hpa, dtype=np.float64)
+    if p.ndim == 1:
+        p = p[None, :, None]
     t = np.arange(nt, dtype=np.float64)[None, None, :]
     z = -7.0 * np.log(p / 1000.0)
     s, c = np.sin(phi), np.cos(phi)

@@ -42,9 +42,7 @@ class TEMDiagnostics:
         if not 0.0 <= float(min_coverage) <= 1.0:
             raise ValueError("min_coverage must lie in [0, 1], got %r" % (min_coverage,))
         if missing == "mask" and q is not None:
-            raise NotImplementedError("missing='mask' does not support tracers (q=): a masked tracer would need a "
-                                      "mask of its own; fill or drop the tracer's missing values, or run it "
-                                      "separately with missing='raise'")
+            self._refuse_masked_tracers()
         self.missing = missing
         self.min_coverage = float(min_coverage)
         # ---- arguments (tem_diagnostics.py:217-236) ----
@@ -118,6 +116,51 @@ class TEMDiagnostics:
         if self.ntrac and plan.status():
             raise RuntimeError("Variable has nans! Spectral zonal averager cannot handle nans; "
                                "please replace or remove them")
+
+    @classmethod
+    def from_model_levels(cls, ua, va, ta, wap, lat_native, *, plev, ps=None, hyam=None, hybm=None, p0_hybrid=1e5,
+                          p_model=None, interp="log", edge="nan", q=None, **kw):
+        """TEM diagnostics of fields on model levels (not in the reference, which takes pressure levels only).
+
+        ``ua va ta wap`` (and the tracers ``q``) are ``[ncol][lev][time]`` on the model's levels, top first; ``plev``
+        [hPa] are the pressure levels to work on.  The source pressure is hybrid (``ps=`` [ncol][time] in Pa with
+        ``hyam=``, ``hybm=`` and ``p0_hybrid=``: p = hyam p0_hybrid + hybm ps) or given point by point
+        (``p_model=``); ``interp`` and ``edge`` are ``interp_to_pressure``'s ``method`` and ``edge``.  All fields are
+        interpolated on the GPU in one engine call, the model-level device copies are released, and the constructor
+        runs on the result with ``plev=`` and everything in ``kw`` (``missing=``, ``min_coverage=``, ``L=`` ...):
+        the object equals ``TEMDiagnostics(*interp_to_pressure([ua, va, ta, wap], plev, ...), lat_native, plev=...)``.
+        Targets below the surface come out NaN: pass ``missing="mask"`` for those (the default raises, as the
+        reference does for NaN input).
+        """
+        import torch
+        from . import vertical
+        if "dims" in kw:
+            raise ValueError("from_model_levels takes [ncol][lev][time] arrays; dims= is not supported")
+        if kw.get("missing", "raise") not in ("raise", "mask"):
+            raise ValueError("missing must be 'raise' or 'mask', got %r" % (kw["missing"],))
+        if kw.get("missing", "raise") == "mask" and q is not None:
+            cls._refuse_masked_tracers()
+        qs = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
+        given = [ua, va, ta, wap] + qs
+        outs, plev_asc = vertical._interp(given, plev, ps=ps, hyam=hyam, hybm=hybm, p0=p0_hybrid, p=p_model,
+                                          method=interp, edge=edge, device=kw.get("device"), on_device=True)
+        # (the model-level device copies died with that call: only the pressure-level tensors are held from here on)
+        raw = not containers.is_labeled(ua)
+        if raw:
+            kw["plev"] = plev_asc
+        obj = cls(*outs[:4], lat_native, q=outs[4:] if qs else None, **kw)
+        # results come back as the kind that went in, as if the interpolated arrays had been handed over on the host
+        v0 = ua if raw else ua.values
+        obj._torch_out = isinstance(v0, torch.Tensor)
+        if not raw:
+            obj._kind = "xarray" if containers.is_xarray(ua) else "labeled"
+        return obj
+
+    @staticmethod
+    def _refuse_masked_tracers():
+        raise NotImplementedError("missing='mask' does not support tracers (q=): a masked tracer would need a "
+                                  "mask of its own; fill or drop the tracer's missing values, or run it "
+                                  "separately with missing='raise'")
 
     # ------------------------------------------------------------------------------------------
     def _config_dims(self):

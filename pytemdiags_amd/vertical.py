@@ -1,0 +1,203 @@
+"""Model levels to pressure levels on the GPU (include/temx_vert.h, kernels_vert.hpp).
+
+The TEM engine takes fields on pressure levels.  Native model output lives on hybrid sigma-pressure levels,
+``p = hyam * p0 + hybm * ps``, different in every column and at every time: ``interp_to_pressure`` is the vertical
+remap in front of the engine, and ``TEMDiagnostics.from_model_levels`` chains the two.
+
+This module validates, moves data and labels; the interpolation itself is one call of ``temxv_interp`` per eight
+fields.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _vert, containers
+
+
+def _values(x):
+    return x.values if containers.is_labeled(x) else x
+
+
+def _check_plev(plev_hpa):
+    plev = np.atleast_1d(np.asarray(plev_hpa, dtype=np.float64))
+    if plev.ndim != 1 or plev.size == 0:
+        raise ValueError("plev_hpa must be a 1-d list of pressure levels in hPa")
+    if not np.all(np.isfinite(plev)) or np.any(plev <= 0):
+        raise ValueError("plev_hpa must be finite and positive")
+    if plev.size > 1 and plev[0] > plev[-1]:
+        plev = plev[::-1].copy()
+    d = np.diff(plev)
+    if np.any(d == 0):
+        raise ValueError("plev_hpa has repeated levels")
+    if np.any(d < 0):
+        raise ValueError("plev_hpa must be sorted (ascending or descending)")
+    return plev
+
+
+def check_hybrid_monotone(hyam, hybm, p0, ps_min, ps_max):
+    """p_k = hyam_k p0 + hybm_k ps is linear in ps, so it increases with k in every column exactly when it does at the
+    smallest and at the largest surface pressure."""
+    for ps in (ps_min, ps_max):
+        pk = hyam * p0 + hybm * ps
+        if not np.all(np.isfinite(pk)) or np.any(np.diff(pk) <= 0):
+            k = int(np.argmax(~(np.diff(pk) > 0))) if pk.size > 1 else 0
+            raise ValueError("hybrid levels are not strictly increasing in pressure at ps = %g Pa (levels %d, %d): "
+                             "model levels must be ordered top first" % (ps, k, k + 1))
+
+
+def _interp(fields, plev_hpa, *, ps=None, hyam=None, hybm=None, p0=1e5, p=None, method="log", edge="nan", device=None,
+            on_device=False):
+    """The work behind ``interp_to_pressure``.  Returns (outputs, ascending plev in hPa); with ``on_device`` the
+    outputs keep device tensors as their values whatever kind came in (``from_model_levels`` feeds them on)."""
+    import torch
+    single = not isinstance(fields, (list, tuple))
+    fl = [fields] if single else list(fields)
+    # ---- everything that can be refused is refused before any device call ----
+    if len(fl) == 0:
+        raise ValueError("no fields given")
+    if method not in _vert.METHODS:
+        raise ValueError("method must be 'log' or 'linear', got %r" % (method,))
+    if edge not in _vert.EDGES:
+        raise ValueError("edge must be 'nan' or 'hold', got %r" % (edge,))
+    if (ps is None) == (p is None):
+        raise ValueError("give exactly one of ps= (hybrid levels, with hyam= and hybm=) and p= (pressure of every point)")
+    hybrid = ps is not None
+    if hybrid and (hyam is None or hybm is None):
+        raise ValueError("hybrid levels (ps=) need hyam= and hybm=")
+    plev = _check_plev(plev_hpa)
+    labeled = [containers.is_labeled(x) for x in fl]
+    if any(labeled) and not all(labeled):
+        raise ValueError("fields must all be of the same kind")
+    for x in fl:
+        if not isinstance(_values(x), (np.ndarray, torch.Tensor)):
+            raise ValueError("fields must be numpy arrays, torch tensors or labelled arrays of them")
+    kind = "raw" if not labeled[0] else ("xarray" if containers.is_xarray(fl[0]) else "labeled")
+    vals = [v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v)) for v in map(_values, fl)]
+    shape = tuple(vals[0].shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("fields must be [ncol][lev] or [ncol][lev][time], got %d dims" % len(shape))
+    for i, v in enumerate(vals):
+        if tuple(v.shape) != shape:
+            raise ValueError("field %d has shape %s, expected %s" % (i, tuple(v.shape), shape))
+        if not v.dtype.is_floating_point:
+            raise ValueError("field %d is not a floating-point array" % i)
+    two_d = len(shape) == 2
+    ncol, nlev = shape[0], shape[1]
+    nt = 1 if two_d else shape[2]
+    if nlev < 2 or ncol < 1 or nt < 1:
+        raise ValueError("fields need at least one column, two levels and one time, got shape %s" % (shape,))
+    pin = _values(ps if hybrid else p)
+    pin = pin if isinstance(pin, torch.Tensor) else torch.as_tensor(np.asarray(pin))
+    if not pin.dtype.is_floating_point:
+        pin = pin.to(torch.float64)
+    want = ((ncol,) if two_d else (ncol, nt)) if hybrid else shape
+    if tuple(pin.shape) != want and not (hybrid and nt == 1 and tuple(pin.shape) in ((ncol,), (ncol, 1))):
+        raise ValueError("%s has shape %s, expected %s" % ("ps" if hybrid else "p", tuple(pin.shape), want))
+    if hybrid:
+        hyam = np.asarray(hyam, dtype=np.float64).ravel()
+        hybm = np.asarray(hybm, dtype=np.float64).ravel()
+        if hyam.shape[0] != nlev or hybm.shape[0] != nlev:
+            raise ValueError("hyam / hybm have %d / %d entries but the fields have %d levels"
+                             % (hyam.shape[0], hybm.shape[0], nlev))
+        if not (np.all(np.isfinite(hyam)) and np.all(np.isfinite(hybm)) and np.isfinite(p0)):
+            raise ValueError("hyam, hybm and p0 must be finite")
+        fin = torch.isfinite(pin)        # a column without a surface pressure comes back NaN; it is no error
+        if bool(fin.any()):
+            lo = float(torch.where(fin, pin, torch.full_like(pin, float("inf"))).min())
+            hi = float(torch.where(fin, pin, torch.full_like(pin, float("-inf"))).max())
+            check_hybrid_monotone(hyam, hybm, float(p0), lo, hi)
+    else:
+        hyam = hybm = None
+
+    # ---- device: contiguous [ncol][lev][time], one dtype; the model-level copies made here die with this frame ----
+    work = torch.float32 if {v.dtype for v in vals} == {torch.float32} else torch.float64
+    if device is None:
+        device = vals[0].device.index if vals[0].is_cuda else 0
+    dev = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+    src = [v.reshape(ncol, nlev, nt).to(device=dev, dtype=work).contiguous() for v in vals]
+    pdt = torch.float32 if pin.dtype == torch.float32 else torch.float64
+    pdev = pin.reshape((ncol, nt) if hybrid else (ncol, nlev, nt)).to(device=dev, dtype=pdt).contiguous()
+    outs = interp_device(src, plev * 100.0, ps=pdev if hybrid else None, p=None if hybrid else pdev, hyam=hyam,
+                         hybm=hybm, p0=float(p0), method=method, edge=edge)
+    del src, pdev
+    if two_d:
+        outs = [o.reshape(ncol, plev.size) for o in outs]
+
+    # ---- the kind that came in ----
+    res = []
+    for x, v, o in zip(fl, vals, outs):
+        if not on_device:
+            o = o.to(v.device) if isinstance(_values(x), torch.Tensor) else o.cpu().numpy()
+        if kind == "raw":
+            res.append(o)
+            continue
+        dims = list(x.dims)
+        coords = {k: c for k, c in dict(getattr(x, "coords", {}) or {}).items() if k != dims[1]}
+        if kind == "labeled":
+            coords = {k: c for k, c in coords.items() if k in dims}
+        dims[1] = "plev"
+        coords["plev"] = plev
+        res.append(containers.make_like("labeled" if on_device else kind, o, tuple(dims), coords,
+                                        getattr(x, "name", None), getattr(x, "attrs", None)))
+    return (res[0] if single else res), plev
+
+
+def interp_device(fields, plev_pa, *, ps=None, p=None, hyam=None, hybm=None, p0=1e5, method="log", edge="nan"):
+    """One ``temxv_interp`` per eight fields.  ``fields``: contiguous device tensors [ncol][nlev][nt] of one dtype;
+    ``ps`` [ncol][nt] or ``p`` [ncol][nlev][nt] on the same device; ``plev_pa`` ascending, in Pa.  Returns new tensors
+    [ncol][nplev][nt]; the call is ordered on the current stream."""
+    import torch
+    lib = _vert.load()
+    f0 = fields[0]
+    ncol, nlev, nt = (int(s) for s in f0.shape)
+    plev_pa = np.ascontiguousarray(plev_pa, dtype=np.float64)
+    nplev = int(plev_pa.shape[0])
+    pin = ps if ps is not None else p
+    for t in list(fields) + [pin]:
+        if not (t.is_cuda and t.device == f0.device and t.is_contiguous()):
+            raise ValueError("interp_device needs contiguous tensors on one device")
+    dts = {torch.float64: _vert.F64, torch.float32: _vert.F32}
+    dp = C.POINTER(C.c_double)
+    with torch.cuda.device(f0.device):
+        outs = [torch.empty((ncol, nplev, nt), dtype=f0.dtype, device=f0.device) for _ in fields]
+        stream = C.c_void_p(torch.cuda.current_stream(f0.device).cuda_stream)
+        for g in range(0, len(fields), _vert.NF_MAX):
+            fs, os_ = fields[g:g + _vert.NF_MAX], outs[g:g + _vert.NF_MAX]
+            sp = (C.c_void_p * len(fs))(*[t.data_ptr() for t in fs])
+            op = (C.c_void_p * len(fs))(*[t.data_ptr() for t in os_])
+            _vert.check(lib.temxv_interp(
+                f0.device.index or 0, len(fs), sp, op, dts[f0.dtype], ncol, nlev, nt, nplev,
+                plev_pa.ctypes.data_as(dp), _vert.P_HYBRID if ps is not None else _vert.P_FIELD,
+                hyam.ctypes.data_as(dp) if ps is not None else None,
+                hybm.ctypes.data_as(dp) if ps is not None else None, float(p0),
+                C.c_void_p(pin.data_ptr()), dts[pin.dtype], _vert.METHODS[method], _vert.EDGES[edge], stream))
+    return outs
+
+
+def interp_to_pressure(fields, plev_hpa, *, ps=None, hyam=None, hybm=None, p0=1e5, p=None, method="log", edge="nan",
+                       device=None):
+    """Interpolate model-level fields to the pressure levels ``plev_hpa`` [hPa] on the GPU.
+
+    ``fields``: one array or a list of arrays laid out ``[ncol][lev][time]`` (or ``[ncol][lev]``), levels top first --
+    numpy arrays, torch tensors or labelled arrays (their second dim is the level dim; the result names it ``plev``).
+    The result is of the same kind, on the target levels, fp32 when every field is fp32 and fp64 otherwise.
+    A descending ``plev_hpa`` is accepted; the result is on ascending levels, like the front end's ``plev``.
+
+    Source pressure, exactly one of
+      * ``ps=`` [ncol][time] in Pa with ``hyam=``, ``hybm=`` [lev] and ``p0=``: hybrid levels,
+        ``p = hyam * p0 + hybm * ps``, formed in fp64 on the device -- no 3-d pressure array exists;
+      * ``p=`` [ncol][lev][time] in Pa: the pressure of every point, for other vertical coordinates.
+
+    ``method``: ``"log"`` linear in ln p (default) or ``"linear"`` linear in p.
+    ``edge``: ``"nan"`` -- a target outside the column's first and last level is NaN; ``"hold"`` -- above the top
+    level and between the bottom level and the surface the nearest level's value is held, below the surface (in
+    ``p=`` mode: below the bottom level) the result is still NaN.  A column whose pressures are not finite and
+    strictly increasing comes back NaN.  NaN below ground is what ``TEMDiagnostics(missing="mask")`` takes.
+
+    Raises ``ValueError`` before any device work for inconsistent arguments, shapes, repeated levels, and hybrid
+    coefficients that are not monotone over the range of ``ps``.
+    """
+    return _interp(fields, plev_hpa, ps=ps, hyam=hyam, hybm=hybm, p0=p0, p=p, method=method, edge=edge,
+                   device=device)[0]
