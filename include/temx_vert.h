@@ -23,8 +23,9 @@
  *                     the bottom value is held, below the surface the result is NaN.  In field mode the surface
  *                     is p_bot: nothing below p_bot is held.
  *   bad columns       a (column, time) whose pressures are not strictly increasing, or not all finite, is NaN at
- *                     every target level.  A non-finite field value reaches only the targets whose bracket
- *                     touches it.
+ *                     every target level.  With TEMXV_LOG so is one with a pressure <= 0 (interface levels
+ *                     with p[0] = 0 have no ln p); TEMXV_LINEAR takes any finite increasing pressures.
+ *                     A non-finite field value reaches only the targets whose bracket touches it.
  * Every input element is read once and every output element written once; src and dst are not copied or
  * re-laid out and must not overlap.  The call is asynchronous and stream ordered.  The small tables of a call (hyam,
  * hybm, plev) are uploaded once per distinct set and kept: the first call with a new set allocates and copies

@@ -11,7 +11,8 @@
 // bracket) is emitted for all fields: value = y_{k-1} + w (y_k - y_{k-1}), w = (x - x_{k-1}) / (x_k - x_{k-1}) in fp64
 // with x = ln p (log) or p (linear), rounded once to the field type.  The bracket search, the logarithms (taken only
 // for brackets that hold a target) and the weights are shared by the NF fields.  Targets above p_0 / below p_bot
-// follow the edge policy; a (column, time) whose pressures are not finite and strictly increasing is NaN throughout.
+// follow the edge policy; a (column, time) whose pressures are not finite and strictly increasing (log: or not all
+// positive) is NaN throughout.
 //
 // Two lane maps, neither of which puts the 64 lanes of a wave into 64 different rows:
 //   vert_time_kernel  lanes run along time (then on into the next column): a wave reads ceil(64 / nt) + 1 row
@@ -55,7 +56,7 @@ __device__ __forceinline__ double vert_hybrid_p(const VertTab& tb, int k, double
 // top level / below the bottom level (a walk over the whole column has both).  A walk that is not the first skips
 // the targets at or above its first level: the walk before it emits them.  pres(k) -> fp64 pressure, load(k, v) fills
 // the NF values of level k, emit(j, f, value) stores one result.  Returns true when the pressures seen are not finite
-// and strictly increasing (the caller then overwrites the column with NaN).
+// and strictly increasing, or (logp) the first of them is not positive (the caller then overwrites the column with NaN).
 template <int NF, class PRES, class LOAD, class EMIT>
 __device__ __forceinline__ bool vert_walk(int nf, int k0, int k1, bool first, bool last, int nplev, const VertTab& tb,
                                           bool logp, bool hold, double psurf, PRES pres, LOAD load, EMIT emit) {
@@ -65,14 +66,14 @@ __device__ __forceinline__ bool vert_walk(int nf, int k0, int k1, bool first, bo
   for (int f = 0; f < NF; ++f) vp[f] = vc[f] = vn[f] = 0.0;
   double pp = pres(k0);
   load(k0, vp);
-  bool bad = !isfinite(pp);
+  bool bad = !isfinite(pp) || (logp && !(pp > 0.0));   // ln p needs p > 0; the levels after the first must increase
   int j = 0;
   if (first) {
     for (; j < nplev && tb.pt[j] < pp; ++j)
 #pragma unroll
       for (int f = 0; f < NF; ++f)
         if (f < nf) emit(j, f, hold ? vp[f] : qnan);
-  } else {   // the first target below this walk's first level
+  } else {   // the first target below this walk's first level (a tie on that level belongs to the walk before)
     int hi = nplev;
     while (j < hi) {
       const int mid = (j + hi) >> 1;

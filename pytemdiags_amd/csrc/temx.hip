@@ -47,12 +47,17 @@ static int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// A failed HIP call is reported through the return code and temx_last_error().  HIP also keeps it as the thread's
+// last error until somebody reads it: it is read here, so that the caller's next HIP call (torch checks
+// hipGetLastError() after its own launches) does not report this library's failure as its own.
 #define HIPCHK(expr)                                                                     \
   do {                                                                                   \
     hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess)                                                                \
+    if (e_ != hipSuccess) {                                                              \
+      (void)hipGetLastError();                                                           \
       return fail(e_ == hipErrorOutOfMemory ? TEMX_ENOMEM : TEMX_EHIP, "%s failed: %s",  \
                   #expr, hipGetErrorString(e_));                                         \
+    }                                                                                    \
   } while (0)
 
 // physical constants of the reference (PyTEMDiags/constants.py:6-14)

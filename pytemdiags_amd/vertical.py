@@ -194,7 +194,9 @@ def interp_to_pressure(fields, plev_hpa, *, ps=None, hyam=None, hybm=None, p0=1e
     ``edge``: ``"nan"`` -- a target outside the column's first and last level is NaN; ``"hold"`` -- above the top
     level and between the bottom level and the surface the nearest level's value is held, below the surface (in
     ``p=`` mode: below the bottom level) the result is still NaN.  A column whose pressures are not finite and
-    strictly increasing comes back NaN.  NaN below ground is what ``TEMDiagnostics(missing="mask")`` takes.
+    strictly increasing comes back NaN; with ``method="log"`` so does one with a pressure <= 0 (interface levels whose
+    first pressure is 0 have no ln p), while ``method="linear"`` takes any finite increasing pressures.  NaN below
+    ground is what ``TEMDiagnostics(missing="mask")`` takes.
 
     Raises ``ValueError`` before any device work for inconsistent arguments, shapes, repeated levels, and hybrid
     coefficients that are not monotone over the range of ``ps``.
