@@ -2,6 +2,7 @@
 // include/temx.h.  gfx950 only.  Build: see csrc/Makefile (hipcc --offload-arch=gfx950).
 #include "../../include/temx.h"
 #include "../../include/temx_vert.h"
+#include "../../include/temx_layout.h"
 
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,7 @@
 #include "side_tables.hpp"
 #include "kernels_miss.hpp"
 #include "kernels_vert.hpp"
+#include "kernels_layout.hpp"
 
 using namespace temx;
 
@@ -2325,6 +2327,32 @@ static int launch_vert_nf(int nf, const void* const* src, void* const* dst, int6
   return launch_vert<T, VERT_NFMAX, HYB>(fp, nf, ncol, nlev, nt, nplev, tb, p0, P, p_f32, logp, hold, map, st);
 }
 
+// ---- re-layout: tile of a launch (kernels_layout.hpp) -----------------------------------------------------------
+// rmax rows of 64 columns fill the 32 KiB tile.  A window of ntb <= rmax times moves whole, with as many levels per
+// tile as fit (the run a column writes is kl * ntb elements); up to 2 rmax it still moves whole, over 32 columns;
+// a longer one is cut into chunks of rmax times, one level per tile.
+static LayoutTile layout_tile(int64_t ncol, int nlev, int64_t ntb, size_t dsz) {
+  LayoutTile tl{};
+  const int rmax = (int)(32 * 1024 / (64 * dsz));
+  tl.tc_shift = 6;
+  if (ntb <= rmax) {
+    tl.tt = (int)ntb;
+    tl.kl = std::max(1, std::min(nlev, rmax / (int)ntb));
+  } else if (ntb <= 2 * rmax) {
+    tl.tc_shift = 5;
+    tl.tt = (int)ntb;
+    tl.kl = 1;
+  } else {
+    tl.tt = rmax;
+    tl.kl = 1;
+  }
+  tl.stride = (tl.kl * tl.tt) | 1;
+  tl.nct = (int)((ncol + (1 << tl.tc_shift) - 1) >> tl.tc_shift);
+  tl.nlt = (nlev + tl.kl - 1) / tl.kl;
+  tl.ntt = (int)((ntb + tl.tt - 1) / tl.tt);
+  return tl;
+}
+
 extern "C" {
 
 int temx_version(void) { return 402; }
@@ -4262,6 +4290,77 @@ int temxv_interp(int device, int nf, const void* const* src_host, void* const* d
   if (dtype == TEMX_F64) return hyb ? TEMXV_GO(double, true) : TEMXV_GO(double, false);
   return hyb ? TEMXV_GO(float, true) : TEMXV_GO(float, false);
 #undef TEMXV_GO
+} TEMX_CATCH
+
+// ---- time-major records to the engine's layout (include/temx_layout.h) ---------------------------
+int temxl_version(void) { return 100; }
+
+int temxl_to_engine(int device, int nf, const void* const* src_host, const int* src_dtype_host, void* const* dst_host,
+                    int dst_dtype, int64_t ncol, int nlev, int64_t nt_src, int64_t t0, int64_t ntb, int flags,
+                    void* stream) try {
+  if (nf < 1 || nf > TEMXL_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", (int)TEMXL_NF_MAX, nf);
+  if (!src_host) return fail(TEMX_EINVAL, "src_host is null");
+  if (!src_dtype_host) return fail(TEMX_EINVAL, "src_dtype_host is null");
+  if (!dst_host) return fail(TEMX_EINVAL, "dst_host is null");
+  if (dst_dtype != TEMX_F64 && dst_dtype != TEMX_F32) return fail(TEMX_EINVAL, "dst_dtype must be TEMX_F64 or TEMX_F32");
+  if (ncol < 1) return fail(TEMX_EINVAL, "ncol must be at least 1");
+  if (nlev < 1) return fail(TEMX_EINVAL, "nlev must be at least 1");
+  if (nt_src < 1) return fail(TEMX_EINVAL, "nt_src must be at least 1");
+  if (ntb < 1) return fail(TEMX_EINVAL, "ntb must be at least 1");
+  if (t0 < 0) return fail(TEMX_EINVAL, "t0 must not be negative");
+  if (nlev > (1 << 20) || nt_src > (int64_t(1) << 31) || ncol > (int64_t(1) << 40))
+    return fail(TEMX_EINVAL, "sizes out of range (ncol, nlev or nt_src)");
+  if (ntb > nt_src || t0 > nt_src - ntb)
+    return fail(TEMX_EINVAL, "t0 + ntb = %lld exceeds nt_src = %lld", (long long)(t0 + ntb), (long long)nt_src);
+  if (flags & ~(int)TEMXL_FLIP_LEV) return fail(TEMX_EINVAL, "flags has unknown bits (0x%x)", (unsigned)flags);
+  const double total = (double)ncol * (double)nlev * (double)nt_src;
+  if (total > 281474976710656.0) return fail(TEMX_EINVAL, "sizes out of range (ncol * nlev * nt_src above 2^48)");
+  const size_t dsz = dst_dtype == TEMX_F64 ? 8 : 4;
+  const size_t src_elems = (size_t)ncol * nlev * nt_src, dst_bytes = (size_t)ncol * nlev * ntb * dsz;
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+  };
+  unsigned src_f32 = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (src_dtype_host[f] != TEMX_F64 && src_dtype_host[f] != TEMX_F32)
+      return fail(TEMX_EINVAL, "src_dtype %d must be TEMX_F64 or TEMX_F32", f);
+    if (src_dtype_host[f] == TEMX_F64 && dst_dtype == TEMX_F32)
+      return fail(TEMX_EINVAL, "src_dtype %d is TEMX_F64 but dst_dtype is TEMX_F32: this call does not narrow", f);
+    if (src_dtype_host[f] == TEMX_F32) src_f32 |= 1u << f;
+    if (!src_host[f]) return fail(TEMX_EINVAL, "src %d is null", f);
+    if (!dst_host[f]) return fail(TEMX_EINVAL, "dst %d is null", f);
+    if ((uintptr_t)src_host[f] % (src_dtype_host[f] == TEMX_F64 ? 8 : 4))
+      return fail(TEMX_EINVAL, "src %d is not aligned to its element size", f);
+    if ((uintptr_t)dst_host[f] % dsz) return fail(TEMX_EINVAL, "dst %d is not aligned to its element size", f);
+  }
+  for (int f = 0; f < nf; ++f)
+    for (int g = 0; g < nf; ++g) {
+      if (overlap(dst_host[f], dst_bytes, src_host[g], src_elems * (src_dtype_host[g] == TEMX_F64 ? 8 : 4)))
+        return fail(TEMX_EINVAL, "dst %d overlaps src %d", f, g);
+      if (g < f && overlap(dst_host[f], dst_bytes, dst_host[g], dst_bytes))
+        return fail(TEMX_EINVAL, "dst %d overlaps dst %d", f, g);
+    }
+  if (ncol > (int64_t(1) << 35)) return fail(TEMX_EUNSUPPORTED, "too many columns for one launch");
+  const LayoutTile tl = layout_tile(ncol, nlev, ntb, dsz);
+  const int64_t grid = (int64_t)tl.nct * nf * tl.nlt * tl.ntt;
+  if (grid >= (int64_t(1) << 32) / LAYOUT_THREADS)   // HIP takes fewer than 2^32 threads per grid dimension
+    return fail(TEMX_EUNSUPPORTED, "too many tiles for one launch (%lld): move the fields or the window in parts", (long long)grid);
+  const size_t lds = ((size_t)1 << tl.tc_shift) * tl.stride * dsz;
+  if (lds > (size_t)LAYOUT_LDS_BYTES) return fail(TEMX_EINTERNAL, "re-layout tile of %zu bytes exceeds its LDS budget", lds);
+  LayoutPtrs fp{};
+  for (int f = 0; f < nf; ++f) fp.src[f] = src_host[f], fp.dst[f] = dst_host[f];
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = S_(stream);
+  const int flip = (flags & TEMXL_FLIP_LEV) ? 1 : 0;
+  if (dst_dtype == TEMX_F64)
+    hipLaunchKernelGGL((layout_to_engine_kernel<uint64_t>), dim3((unsigned)grid), dim3(LAYOUT_THREADS), lds, st, fp, nf,
+                       src_f32, ncol, nlev, t0, ntb, flip, tl);
+  else
+    hipLaunchKernelGGL((layout_to_engine_kernel<uint32_t>), dim3((unsigned)grid), dim3(LAYOUT_THREADS), lds, st, fp, nf,
+                       src_f32, ncol, nlev, t0, ntb, flip, tl);
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
 } TEMX_CATCH
 
 }  // extern "C"

@@ -18,7 +18,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, containers
+from . import _lib, containers, layout
 from .constants import P0, Om
 from .sph_zonal_mean import sph_zonal_averager
 
@@ -35,7 +35,9 @@ class TEMDiagnostics:
     def __init__(self, ua, va, ta, wap, lat_native, q=None, p0=P0, zm_dlat=1, L=50,
                  dim_names=DEFAULT_DIMS, grid_name=None, zm_grid_name=None, map_save_dest=None,
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
-                 *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5):
+                 *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None):
+        # ---- blocked run over the time axis (not in the reference): checked before anything touches the device ----
+        self.time_block = layout.check_time_block(time_block)
         # ---- missing-value mode (not in the reference): checked before anything touches the device ----
         if missing not in ("raise", "mask"):
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (missing,))
@@ -77,45 +79,126 @@ class TEMDiagnostics:
             self.ZM.sph_compute_matrices(overwrite=overwrite_map)
         self._zonal_mean = self.ZM.sph_zonal_mean
 
-        # ---- the whole numeric pipeline: one engine call (tem_diagnostics.py:252-259) ----
+        # ---- the whole numeric pipeline: one engine call (tem_diagnostics.py:252-259), or one per time block ----
         plan = self.ZM._plan
-        plan.set_tem(self.NLEV, self.NT, self._p_np, float(self.p0))
+        self._eddy = None
+        self._theta = None
+        self._out_file = None
+        self._teddy = [None] * self.ntrac
+        self._last_tracer = None
+        self._after_launch = None
+        self.block_timing = None
+        if self.time_block is None:
+            plan.set_tem(self.NLEV, self.NT, self._p_np, float(self.p0))
+            self._res, self._zon, self._cov, self._tres, self._tzon = self._run_block(
+                plan, self._dev_fields, self._dev_q, self.NT)
+        else:
+            self._run_blocked(plan)
+
+    def _run_block(self, plan, fields, qs, nt):
+        """One engine run over ``nt`` snapshots in engine layout (``plan.set_tem`` has been called for them):
+        the whole record in the default mode, one time block under ``time_block=``.
+        -> (results, zonal intermediates, coverage or None, tracer results, tracer zonal intermediates)."""
         # (class-sum forms: the first tracer, when there is one, shares the sweep of the fields, temx_tem_tracer_run;
         #  single sweep: the tracers follow the TEM run in pairs, temx_tracers_run)
         fused = None
         if self.ntrac and not plan.single_sweep:
-            self._res, self._zon, *fused = plan.tem_tracer_run(*self._dev_fields, self._dev_q[0], want_zonal=True)
+            res, zon, *fused = plan.tem_tracer_run(*fields, qs[0], want_zonal=True)
         else:
-            self._res, self._zon = plan.tem_run(*self._dev_fields, want_zonal=True)
+            res, zon = plan.tem_run(*fields, want_zonal=True)
+        if self._after_launch is not None:                  # blocked run: the next block goes up behind this one
+            self._after_launch()
         # missing="mask": coverage of this run on the zonal grid (the averager's later calls reuse the plan)
-        self._cov = plan.coverage().reshape(self.ZM_N, self.NLEV, self.NT) if missing == "mask" else None
+        cov = plan.coverage().reshape(self.ZM_N, self.NLEV, nt) if self.missing == "mask" else None
         if plan.status():                                   # sph_zonal_mean.py:219-221
             raise RuntimeError("Variable has nans! Spectral zonal averager cannot handle nans; "
                                "please replace or remove them")
-        self._eddy = None
-        self._theta = None
-        self._out_file = None
         # ---- tracers (tem_diagnostics.py:532-538, 560-570, 602-611): one engine call each ----
-        self._tres, self._tzon, self._teddy = [], [], [None] * self.ntrac
-        self._last_tracer = None
+        tres_all, tzon_all = [], []
         if self.ntrac and plan.single_sweep:
             # the list of tracers in one engine call: two per sweep, (q1, q2, v, omega) read once
-            for tres, tzon in plan.tracers_run(self._dev_q, self._dev_fields[1], self._dev_fields[3], want_zonal=True):
-                self._tres.append(tres)
-                self._tzon.append(tzon)
+            for tres, tzon in plan.tracers_run(qs, fields[1], fields[3], want_zonal=True):
+                tres_all.append(tres)
+                tzon_all.append(tzon)
             self._last_tracer = self.ntrac - 1
         else:
             for i in range(self.ntrac):
                 if i == 0 and fused is not None:
                     tres, tzon = fused
                 else:
-                    tres, tzon = plan.tracer_run(self._dev_q[i], self._dev_fields[1], self._dev_fields[3], want_zonal=True)
-                self._tres.append(tres)
-                self._tzon.append(tzon)
+                    tres, tzon = plan.tracer_run(qs[i], fields[1], fields[3], want_zonal=True)
+                tres_all.append(tres)
+                tzon_all.append(tzon)
                 self._last_tracer = i
         if self.ntrac and plan.status():
             raise RuntimeError("Variable has nans! Spectral zonal averager cannot handle nans; "
                                "please replace or remove them")
+        return res, zon, cov, tres_all, tzon_all
+
+    def _run_blocked(self, plan):
+        """``time_block=``: every TEM step is independent per snapshot (the tail couples latitude and pressure only),
+        so the record runs in the blocks of ``layout.time_blocks`` and the results are gathered on the zonal grid at
+        ``[..., t0:t1]``.  The native-grid fields are not kept."""
+        import torch
+        blocks = layout.time_blocks(self.NT, self.time_block)
+        src = self._block_source
+        src.start(blocks)
+        big = None
+        cur = None
+        try:
+            for n, (t0, t1) in enumerate(blocks):
+                ntb = t1 - t0
+                fs = src.get(n)
+                if ntb != cur:
+                    plan.set_tem(self.NLEV, ntb, self._p_np, float(self.p0))
+                    cur = ntb
+                self._after_launch = lambda n=n: src.after_launch(n)
+                out = self._run_block(plan, fs[:4], fs[4:], ntb)
+                src.done(n)
+                del fs
+                if len(blocks) == 1:
+                    big = out
+                    break
+                if big is None:
+                    def whole(x):
+                        return torch.empty(tuple(x.shape[:-1]) + (self.NT,), dtype=x.dtype, device=x.device)
+                    big = (whole(out[0]), whole(out[1]), None if out[2] is None else whole(out[2]),
+                           [whole(x) for x in out[3]], [whole(x) for x in out[4]])
+                big[0][..., t0:t1] = out[0]
+                big[1][..., t0:t1] = out[1]
+                if out[2] is not None:
+                    big[2][..., t0:t1] = out[2]
+                for dst, x in zip(big[3] + big[4], out[3] + out[4]):
+                    dst[..., t0:t1] = x
+                del out
+        finally:
+            self._after_launch = None
+            src.close()
+            self.block_timing = src.timing
+            self._block_source = None
+        self._res, self._zon, self._cov, self._tres, self._tzon = big
+        self._last_tracer = None
+
+    def _refuse_native(self, what):
+        if self.time_block is not None:
+            raise RuntimeError("%s is not available with time_block=%d: a blocked run keeps no native-grid fields; "
+                               "run without time_block for native outputs" % (what, self.time_block))
+
+    def _input_field(self, i, name):
+        self._refuse_native(name)
+        return self._dev_fields[i]
+
+    # the inputs on the device, [ncol][plev][time] in the work dtype (a whole run keeps them, a blocked run does not)
+    ua = property(lambda s: s._input_field(0, "ua"))
+    va = property(lambda s: s._input_field(1, "va"))
+    ta = property(lambda s: s._input_field(2, "ta"))
+    wap = property(lambda s: s._input_field(3, "wap"))
+
+    @property
+    def input_path(self):
+        """How the inputs reached the engine's layout: ``"relayout"`` (time-major input, the GPU re-layout of
+        ``layout.to_engine_layout``) or ``"torch"`` (any other dims order: permute and contiguous)."""
+        return self._input_path
 
     @classmethod
     def from_model_levels(cls, ua, va, ta, wap, lat_native, *, plev, ps=None, hyam=None, hybm=None, p0_hybrid=1e5,
@@ -203,7 +286,7 @@ class TEMDiagnostics:
         if all(labeled):
             self._kind = "xarray" if containers.is_xarray(self._in["ua"]) else "labeled"
 
-        vals = {}
+        vals, raw, tmajor = {}, {}, {}
         for var, dat in self._in.items():
             if self._kind == "raw":
                 if not (isinstance(dat, np.ndarray) or isinstance(dat, torch.Tensor)):
@@ -222,6 +305,8 @@ class TEMDiagnostics:
             if len(ddims) < 2 or len(ddims) > 3:                                              # :326-329
                 raise RuntimeError("Input data has {0} dims, expected either 2 ({1}, {2}) or 3 ({1}, {2}, {3})"
                                    .format(len(ddims), self.ncolname, self.plevname, self.timename))
+            raw[var] = v
+            tmajor[var] = layout.is_time_major(ddims, self.data_dims, v)
             t = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
             if self.timename not in ddims:                  # 2-D input: add a length-1 time axis (:332-335)
                 t = t.unsqueeze(-1)
@@ -251,8 +336,16 @@ class TEMDiagnostics:
                     var, tuple(vals[var].shape), tuple(vals["ua"].shape)))
 
         # ---- pressure direction: model top first (tem_diagnostics.py:369-382) ----
-        if plev[0] > plev[-1]:
-            vals = {k: torch.flip(v, dims=(1,)) for k, v in vals.items()}
+        # (time-major input: the GPU re-layout reverses the levels on its way, no flipped copy is made)
+        relayout = all(tmajor.values()) and all(v.dtype in (torch.float32, torch.float64) for v in vals.values())
+        if relayout and self.time_block is None:
+            work_name = "float32" if all(v.dtype == torch.float32 for v in vals.values()) else "float64"
+            relayout = layout.WHOLE_RUN_KERNEL[work_name]
+        self._input_path = "relayout" if relayout else "torch"
+        flip = bool(plev[0] > plev[-1])
+        if flip:
+            if not relayout:
+                vals = {k: torch.flip(v, dims=(1,)) for k, v in vals.items()}
             plev = plev[::-1].copy()
         self.plev = plev
         self.time = time
@@ -281,10 +374,37 @@ class TEMDiagnostics:
                            else (self._device.index or 0))
         self._torch_out = isinstance(self._in["ua"], torch.Tensor) or (
             self._kind != "raw" and isinstance(self._in["ua"].values, torch.Tensor))
-        self._dev_fields = [vals[k].to(device=dev, dtype=work).contiguous() for k in ("ua", "va", "ta", "wap")]
-        self.ua, self.va, self.ta, self.wap = self._dev_fields
         self._work_dtype = work
-        self._dev_q = [vals["q{}".format(i)].to(device=dev, dtype=work).contiguous() for i in range(self.ntrac)]
+        names = ["ua", "va", "ta", "wap"] + ["q{}".format(i) for i in range(self.ntrac)]
+        self._block_source = None
+        if self.time_block is not None:
+            # blocked run: nothing is made resident here, _run_blocked brings one block at a time
+            self._dev_fields, self._dev_q = None, None
+            srcs = [raw[k] for k in names]
+            if not relayout:
+                self._block_source = layout.TorchBlocks([vals[k] for k in names], dev, work)
+            elif all(isinstance(x, np.ndarray) or not x.is_cuda for x in srcs):
+                self._block_source = layout.HostBlocks(srcs, dev, flip, work)
+            else:
+                srcs = [(x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(dev) for x in srcs]
+                self._block_source = layout.DeviceBlocks(srcs, flip, work)
+        elif relayout:
+            # time-major input goes up as it lies; the re-layout makes the engine's copy, flip and widening included.
+            # Fields already on the device move in one launch; a host field goes up, is re-laid out and released
+            # before the next one, so the peak is the record plus one field, not twice the record.
+            up = [raw[k] if isinstance(raw[k], torch.Tensor) else torch.as_tensor(np.asarray(raw[k])) for k in names]
+            if all(x.is_cuda and x.device == dev for x in up):
+                outs = layout.to_engine_layout(up, flip_lev=flip, dtype=work)
+            else:
+                with torch.cuda.device(dev):
+                    outs = list(torch.empty((len(up), self.NCOL, self.NLEV, self.NT), dtype=work, device=dev).unbind(0))
+                for x, o in zip(up, outs):
+                    layout.to_engine_layout([x.to(dev)], flip_lev=flip, dtype=work, out=[o])
+            del up
+            self._dev_fields, self._dev_q = outs[:4], outs[4:]
+        else:
+            self._dev_fields = [vals[k].to(device=dev, dtype=work).contiguous() for k in ("ua", "va", "ta", "wap")]
+            self._dev_q = [vals["q{}".format(i)].to(device=dev, dtype=work).contiguous() for i in range(self.ntrac)]
         self._tracer_names = [getattr(x, "name", None) for x in self.q]
 
     # ------------------------------------------------------------------------------------------
@@ -318,6 +438,7 @@ class TEMDiagnostics:
         return self._wrap(self._res[_lib.RESULT_NAMES.index(name)], name, src_var)
 
     def _native(self, name, src_var):
+        self._refuse_native(name)
         if self._eddy is None:                        # lazily materialised [ncol][plev][time] fields
             self._eddy = self.ZM._plan.tem_eddy(*self._dev_fields)
         return self._wrap(self._eddy[name], name, src_var, native=True)
@@ -327,6 +448,10 @@ class TEMDiagnostics:
         tem_diagnostics.py:420-433) in blocks of columns instead of materialising ``[ncol][plev][time]``
         arrays whole: yields ``(col0, col1, {name: ndarray[col1 - col0, plev, time]})`` with the dtype the
         corresponding property would have.  Device memory: one block of seven arrays."""
+        self._refuse_native("iter_native")
+        return self._iter_native(names, chunk_cols)
+
+    def _iter_native(self, names, chunk_cols):
         chunk = max(16, (int(chunk_cols) // 16) * 16)
         src = {"up": "ua", "vp": "va", "thetap": "ta", "wapp": "wap", "upvp": "ua", "upwapp": "ua", "vptp": "va"}
         for c0 in range(0, self.NCOL, chunk):
@@ -377,6 +502,7 @@ class TEMDiagnostics:
         return [self._wrap(self._tzon[i][k], name, src(i), force64=force64) for i in range(self.ntrac)]
 
     def _tnative(self, name, src):
+        self._refuse_native(name)
         out = []
         for i in range(self.ntrac):
             if self._teddy[i] is None:
@@ -403,6 +529,7 @@ class TEMDiagnostics:
         """theta = T (p0/p)^k (tem_diagnostics.py:498); recovered as thetap + its native zonal mean
         would cost a sweep, so it is formed from the same per-level scale the engine fuses."""
         import torch
+        self._refuse_native("theta")
         if self._theta is None:
             from .constants import k
             scale = torch.as_tensor((float(self.p0) / self._p_np) ** k, device=self._dev_fields[2].device)
@@ -461,6 +588,8 @@ class TEMDiagnostics:
         filename = "{}TEM_{}_{}_L{}.nc".format(prefix, self.ZM.grid_name, self.ZM.grid_out_name, self.L)
         self._out_file = "{}/{}".format(loc, filename)
         names = {}
+        if include_attrs:
+            self._refuse_native("to_netcdf(include_attrs=True)")
         if include_attrs:   # (sic) key 'wawpp' as in tem_diagnostics.py:1011
             names = {"ub": "ub", "up": "up", "vb": "vb", "vp": "vp", "thetab": "thetab", "thetap": "thetap",
                      "wapb": "wapb", "wawpp": "wapp", "upvp": "upvp", "upvpb": "upvpb", "upwapp": "upwapp",
