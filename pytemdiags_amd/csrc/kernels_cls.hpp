@@ -10,7 +10,7 @@
 // the sweeps turn from MFMA bound into pure HBM streams (one v_add / a few VALU ops per element).
 // The mirror-paired sweeps of kernels_sym.hpp are the special case of one member per side.
 //
-// Tables (built on the host, temx.hip build_classes):
+// Tables (built on the host, class_tables.hpp build_classes):
 //   classes are sorted by (members N, members S) so that the 4 classes of a class-group (the MFMA
 //   k dimension) have equal counts; a group is walked in batches of CLS_MB member rows per class,
 //   first its northern batches, then its southern ones.
@@ -38,6 +38,7 @@
 // complete).  The large-L class path (PROJ = false) stores all seven sums (records of 7 pairs).
 #pragma once
 #include "kernels_sym.hpp"
+#include "shared_defs.hpp"
 
 namespace temx {
 
@@ -81,9 +82,6 @@ __device__ int64_t temx_lab_ngr;
 #define TEMX_CSUM_REC(grp, dt, ndt) ((int64_t)(grp) * (ndt) + (dt))
 #endif
 
-constexpr int CLS_MB = 4;                     // member rows per class and batch
-constexpr int CLS_PADB = 10;                  // batches of padding behind crow (index loads run up to PD + 1 ahead)
-
 // compile-time unrolled loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
 template <int N, int I = 0, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -93,8 +91,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 constexpr int CLS_ROWMASK = 0x07FFFFFF;
-constexpr int CLS_HASPAD_BIT = 1 << 27;       // the batch has at least one padding entry (set in all its entries)
-constexpr int CLS_SOUTH = 1, CLS_FIRST = 2, CLS_LAST = 4;   // flags, stored at bit 28
+// (CLS_MB, CLS_PADB, CLS_HASPAD_BIT and the flags CLS_SOUTH / CLS_FIRST / CLS_LAST: shared_defs.hpp)
 
 template <int KMAX>
 __global__ void cls_basis_kernel(const double* __restrict__ xc, int64_t ncls, int64_t ncls_pad, int K, int TBS,

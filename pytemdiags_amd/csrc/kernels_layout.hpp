@@ -19,6 +19,7 @@
 // dst[f][0 .. ncol * nlev * ntb).  All global offsets are int64_t.
 #pragma once
 #include "kernels.hpp"
+#include "shared_defs.hpp"
 
 namespace temx {
 
@@ -32,14 +33,7 @@ struct LayoutPtrs {
   void* dst[LAYOUT_NFMAX];
 };
 
-// tile of a launch (host: layout_tile)
-struct LayoutTile {
-  int tc_shift;   // TC = 1 << tc_shift columns, 32 or 64
-  int kl;         // destination levels per tile
-  int tt;         // times per tile (== ntb unless kl == 1)
-  int stride;     // LDS elements per column, odd, >= kl * tt
-  int nct, nlt, ntt;   // tiles along ncol, nlev, ntb
-};
+// tile of a launch: LayoutTile (shared_defs.hpp), chosen by layout_tile (launch_shapes.hpp)
 
 template <typename U>
 struct LayoutWide;   // the narrower source of U, if there is one

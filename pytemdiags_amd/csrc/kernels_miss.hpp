@@ -143,7 +143,7 @@ miss_project_kernel(FieldPtrs<NF> fp, int64_t N, int64_t D, int K, int NE, const
   }
 }
 
-// Tables of the per-d systems (built on the host, temx.hip miss_setup).
+// Tables of the per-d systems (built on the host, host_math.hpp miss_tables).
 struct MissTables {
   const double* G2;     // [K][K]   Q^T Q
   const double* Zq;     // [NQ][K]  Q-basis rows at the Gauss nodes: Zq[q][j] = sum_l Y_l(x_q) T[l][j]

@@ -1217,7 +1217,7 @@ sweep_os2_kernel(FieldPtrs<4> fp, int64_t D, int K, int KX, const double* __rest
   // differs from its fp64 run by 5e-6) allows n <= 2e-6 x 2^24 = 33 -- in units of the eddy amplitude; a flux mean
   // is compared in units of the flux, a tenth of A^2 for waves in quadrature, which takes the side to the 8 members
   // of a cubed sphere (n 2^-24 = 4.8e-7; measured 5e-6 of the flux): the host cuts the long class sides of an fp32
-  // plan to TEMX_F32_SIDE_CAP = 8 members (temx.hip, above build_classes, with the measurements) and this kernel is
+  // plan to TEMX_F32_SIDE_CAP = 8 members (class_tables.hpp, above build_classes, with the measurements) and this kernel is
   // not launched on a table with a side beyond 8 x that.  Everything from the side means on is fp64 as before.  It
   // takes the conversions and the quarter-rate fp64 VALU work out of the inner loop.
   using AT = typename std::conditional<(sizeof(T) == 4 && TEMX_OS2_ACC32), float, double>::type;

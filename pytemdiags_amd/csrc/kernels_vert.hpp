@@ -24,11 +24,11 @@
 //                     LDS still fill the workgroup -- and writes the output span back as one contiguous run.
 #pragma once
 #include "kernels.hpp"
+#include "shared_defs.hpp"
 
 namespace temx {
 
 constexpr int VERT_NFMAX = 8;
-constexpr int VERT_THREADS = 256;
 
 template <int NF>
 struct VertPtrs {
@@ -214,15 +214,7 @@ __device__ __forceinline__ void vert_span_out(E* __restrict__ g, const E* s, int
   }
 }
 
-// LDS of a workgroup (host: vert_slab_shape): [int bad[VERT_THREADS]] [fp64 P image, field mode] [NF input images]
-// [NF output images]; every image starts on a 16-byte boundary.
-struct VertSlab {
-  int cw;        // columns per workgroup
-  int nseg;      // walks (lanes) per (column, time)
-  int seg;       // brackets per walk
-  int in_stride, out_stride;   // elements per column in the LDS images (odd)
-  int in_img, out_img, p_img;  // bytes per image
-};
+// LDS of a workgroup: VertSlab (shared_defs.hpp), filled in by vert_slab_shape (launch_shapes.hpp)
 
 template <typename T, int NF, bool HYB>
 __global__ void __launch_bounds__(VERT_THREADS)

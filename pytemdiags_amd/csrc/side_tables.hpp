@@ -4,9 +4,13 @@
 // Same entry format (row | flags << 28 | has-padding << 27, padding entries negative); CLS_FIRST / CLS_LAST mark the
 // first / last batch of the group ON THAT SIDE; a group without members on a side gets one batch of padding
 // entries, so both tables have every group.  gfirst[g] = first batch of group g, gfirst[ngroups] = batches.
-#pragma once
+#ifndef TEMX_SIDE_TABLES_HPP
+#define TEMX_SIDE_TABLES_HPP
+#include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#include "shared_defs.hpp"
 
 namespace temx {
 
@@ -15,9 +19,8 @@ struct SideTables {
   std::vector<int> gfirst[2];   // [ngroups + 1]
 };
 
-inline void build_side_tables(const std::vector<int>& crow, const std::vector<int>& gbatch0, int64_t ngroups, int mb,
-                              int padb, int south_flag, int first_flag, int last_flag, int haspad_bit, SideTables& out) {
-  const int per = 4 * mb;
+inline void build_side_tables(const std::vector<int>& crow, const std::vector<int>& gbatch0, int64_t ngroups, SideTables& out) {
+  const int per = 4 * CLS_MB;
   for (int side = 0; side < 2; ++side) {
     out.crow[side].clear();
     out.gfirst[side].assign((size_t)ngroups + 1, 0);
@@ -26,19 +29,19 @@ inline void build_side_tables(const std::vector<int>& crow, const std::vector<in
     std::vector<int> mine[2];
     for (int b = gbatch0[(size_t)g]; b < gbatch0[(size_t)g + 1]; ++b) {
       const int fl = (crow[(size_t)b * per] >> 28) & 7;
-      mine[(fl & south_flag) ? 1 : 0].push_back(b);
+      mine[(fl & CLS_SOUTH) ? 1 : 0].push_back(b);
     }
     for (int side = 0; side < 2; ++side) {
       std::vector<int>& t = out.crow[side];
       out.gfirst[side][(size_t)g] = (int)(t.size() / per);
       const size_t nb = mine[side].size();
       if (nb == 0) {
-        const int fl = first_flag | last_flag;
-        for (int e = 0; e < per; ++e) t.push_back((int)0x80000000 | (fl << 28) | haspad_bit);
+        const int fl = CLS_FIRST | CLS_LAST;
+        for (int e = 0; e < per; ++e) t.push_back((int)0x80000000 | (fl << 28) | CLS_HASPAD_BIT);
         continue;
       }
       for (size_t i = 0; i < nb; ++i) {
-        const int fl = (i == 0 ? first_flag : 0) | (i + 1 == nb ? last_flag : 0);
+        const int fl = (i == 0 ? CLS_FIRST : 0) | (i + 1 == nb ? CLS_LAST : 0);
         for (int e = 0; e < per; ++e) {
           const int ent = crow[(size_t)mine[side][i] * per + e];
           t.push_back((ent & ~(7 << 28)) | (fl << 28));        // row, padding sign and has-padding bit stay
@@ -48,8 +51,10 @@ inline void build_side_tables(const std::vector<int>& crow, const std::vector<in
   }
   for (int side = 0; side < 2; ++side) {
     out.gfirst[side][(size_t)ngroups] = (int)(out.crow[side].size() / per);
-    out.crow[side].resize(out.crow[side].size() + (size_t)padb * per, (int)0x80000000);
+    out.crow[side].resize(out.crow[side].size() + (size_t)CLS_PADB * per, (int)0x80000000);
   }
 }
 
 }  // namespace temx
+
+#endif

@@ -27,10 +27,13 @@
 #include "kernels_op.hpp"
 #include "kernels_op2.hpp"
 #include "kernels_osc.hpp"
-#include "side_tables.hpp"
 #include "kernels_miss.hpp"
 #include "kernels_vert.hpp"
 #include "kernels_layout.hpp"
+// host code without HIP: the tables, matrices and launch shapes of a plan
+#include "class_tables.hpp"
+#include "host_math.hpp"
+#include "launch_shapes.hpp"
 
 using namespace temx;
 
@@ -62,9 +65,6 @@ static int fail(int code, const char* fmt, ...) {
     }                                                                                    \
   } while (0)
 
-// physical constants of the reference (PyTEMDiags/constants.py:6-14)
-static const double kR = 287.058, kCp = 1004.64, kOm = 7.29212e-5;
-
 // ------------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------------
@@ -87,10 +87,6 @@ struct DevBuf {
     bytes = 0;
   }
   double* d() const { return static_cast<double*>(p); }
-};
-
-struct Split {
-  int ndt = 0, nsplit = 0, grid = 0, dpw = 4;   // dpw: d-tiles per workgroup
 };
 
 struct TimedLaunch {
@@ -281,35 +277,6 @@ static int alloc_write_stream(DevBuf& b, size_t need) {
   return TEMX_OK;
 }
 
-// How to cut (d-tiles x chunk range) into wave-sized work so that `slots` workgroup slots
-// (CUs x resident workgroups) are evenly filled.  Smaller nsplit is preferred on near-ties
-// (fewer partial slabs to write and re-read).
-static Split choose_split(int64_t D, int64_t nchunk, int slots, int dpw = 4, int minchunk = 4) {
-  Split s;
-  s.dpw = dpw;
-  s.ndt = (int)((D + 15) / 16);
-  const int ndq = (s.ndt + dpw - 1) / dpw;    // a workgroup owns dpw consecutive d-tiles
-  int64_t maxsplit = std::max<int64_t>(1, nchunk / minchunk);
-  maxsplit = std::min<int64_t>(maxsplit, std::max<int64_t>(1, (int64_t)4 * slots / ndq + 1));
-  maxsplit = std::min<int64_t>(maxsplit, 4096);
-  double best = -1.0;
-  int bestn = 1;
-  for (int n = 1; n <= maxsplit; ++n) {
-    const int64_t nwg = (int64_t)ndq * n;
-    const int64_t rounds = (nwg + slots - 1) / slots;
-    const double eff = (double)nwg / (double)(rounds * slots);
-    if (eff > best * 1.02) {
-      best = eff;
-      bestn = n;
-    }
-  }
-  s.nsplit = bestn;
-  const int64_t nwg = (int64_t)ndq * s.nsplit;
-  s.grid = (int)(((nwg + 7) / 8) * 8);
-  return s;
-}
-
-
 // hipFuncSetAttribute is per device: remember, per kernel instantiation, which devices have the
 // dynamic-LDS limit raised (a process may own plans on several GPUs).
 static int lds_attr_once(std::atomic<uint64_t>& done, int device, const void* fn, int bytes) {
@@ -320,21 +287,8 @@ static int lds_attr_once(std::atomic<uint64_t>& done, int device, const void* fn
   return TEMX_OK;
 }
 
-
-// 4x4 MFMA A-operand blocks of a row-major R x K matrix: blk[rb][t][k*4+i] = A[4rb+i][4t+k], zero padded
-static int upload_blocks(DevBuf& dst, const double* A, int R, int K, int TB) {
-  const int nrb = (R + 3) / 4;
-  std::vector<double> blk((size_t)nrb * TB * 16, 0.0);
-  for (int rb = 0; rb < nrb; ++rb)
-    for (int t = 0; t < TB; ++t)
-      for (int k = 0; k < 4; ++k)
-        for (int i = 0; i < 4; ++i) {
-          const int r = 4 * rb + i, col = 4 * t + k;
-          if (r < R && col < K) blk[((size_t)rb * TB + t) * 16 + k * 4 + i] = A[(size_t)r * K + col];
-        }
-  return upload(dst, blk.data(), blk.size() * 8);
-}
-
+template <typename T>
+static int upload(DevBuf& b, const std::vector<T>& v) { return upload(b, v.data(), v.size() * sizeof(T)); }
 static int os_upload_blocks(temx_plan* pl);
 
 static int set_ginv(temx_plan* pl, const double* Gi_host) {
@@ -343,10 +297,10 @@ static int set_ginv(temx_plan* pl, const double* Gi_host) {
   if (pl->os_built)
     if (int rc = os_upload_blocks(pl)) return rc;
   if (pl->K > 64) return TEMX_OK;
-  // Ginv padded to 4*TB rows: upload_blocks wants TB row-blocks
+  // Ginv padded to 4*TB rows: pack_blocks4 wants TB row-blocks
   std::vector<double> Gp((size_t)4 * pl->TB * pl->K, 0.0);
   std::copy(Gi_host, Gi_host + (size_t)pl->K * pl->K, Gp.begin());
-  return upload_blocks(pl->gblk, Gp.data(), 4 * pl->TB, pl->K, pl->TB);
+  return upload(pl->gblk, pack_blocks4(Gp.data(), 4 * pl->TB, pl->K, pl->TB));
 }
 
 constexpr size_t kMaxTimedLaunches = 256;   // enough for an average; bounds the events a long run creates
@@ -619,50 +573,9 @@ static int project_all(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int64_
   return TEMX_OK;
 }
 
-
 // ------------------------------------------------------------------------------------------------
-// mirror pairing of an equatorially symmetric grid (kernels_sym.hpp)
+// latitude classes and mirror pairs: the tolerance, and the work cuts on the device (class_tables.hpp)
 // ------------------------------------------------------------------------------------------------
-static double sym_tol_deg(double dflt);
-
-// Every column with lat > tol must have a partner with the opposite latitude (any longitude);
-// |lat| <= tol are equator columns (pairs without a southern partner).  Returns false if the grid is
-// not symmetric.  Pairs are ordered by their northern row so one operand still streams.
-static bool find_mirror_pairs(const double* lat, int64_t N, std::vector<int>& rowN, std::vector<int>& rowS, double tol_dflt) {
-  if (N >= ((int64_t)1 << 31)) return false;
-  // Two columns pair up when their latitudes are opposite to within `tol` degrees; the pair is then
-  // treated as sitting exactly at +-(northern latitude), which perturbs the operator by
-  // O(L^2 tol).  The default keeps that below the fp64 parity tolerance; TEMX_SYM_TOL_DEG widens
-  // it for grids whose files carry noisier latitudes.
-  const double tol = sym_tol_deg(tol_dflt);
-  std::vector<int> north, south, eq;
-  for (int64_t i = 0; i < N; ++i) {
-    if (!(std::fabs(lat[i]) <= 90.0 + 1e-9)) return false;
-    if (lat[i] > tol) north.push_back((int)i);
-    else if (lat[i] < -tol) south.push_back((int)i);
-    else eq.push_back((int)i);
-  }
-  if (north.size() != south.size()) return false;
-  std::stable_sort(north.begin(), north.end(), [&](int a, int b) { return lat[a] < lat[b]; });
-  std::stable_sort(south.begin(), south.end(), [&](int a, int b) { return -lat[a] < -lat[b]; });
-  std::vector<std::pair<int, int>> pairs;
-  pairs.reserve(north.size() + eq.size());
-  for (size_t k = 0; k < north.size(); ++k) {
-    if (std::fabs(lat[north[k]] + lat[south[k]]) > tol) return false;
-    pairs.emplace_back(north[k], south[k]);
-  }
-  for (int e : eq) pairs.emplace_back(e, -1);
-  std::sort(pairs.begin(), pairs.end());
-  rowN.resize(pairs.size());
-  rowS.resize(pairs.size());
-  for (size_t k = 0; k < pairs.size(); ++k) {
-    rowN[k] = pairs[k].first;
-    rowS[k] = pairs[k].second;
-  }
-  return true;
-}
-
-
 static double sym_tol_deg(double dflt) {
   // Two columns share a latitude class (or pair up) when their |lat| agree to within `tol` degrees; the members are
   // then treated as sitting exactly at the class latitude (the mean of its members), which perturbs a basis row by
@@ -680,265 +593,26 @@ static double sym_tol_deg(double dflt) {
   return tol;
 }
 
-// Latitude classes (kernels_cls.hpp).  Returns false when the grid has too few columns per class
-// for the class sweeps to pay (the paired or generic sweeps are used instead).
-struct ClassTables {
-  std::vector<int> crow;        // [nbatch + 2][4][CLS_MB]
-  std::vector<double> xc;       // [4 * (ngroups + 1)] cos(colat) of the class latitude
-  std::vector<int> gbatch0;     // [ngroups + 1]
-  std::vector<double> cnt;      // [ngroups][2 sides][4 classes] member counts
-  int64_t ncls = 0, ngroups = 0, nbatch = 0;
-  int64_t max_side = 0;         // members of the longest class side
-};
-
-// Longest class side of a plan for fp32 fields (TEMX_LAT_TOL_F32).  sweep_os2_kernel adds the members of a side into
-// ONE fp32 accumulator in sequence: with terms of size <= A (the eddy amplitude) the partial sum after k members is
-// <= k A and the k-th addition rounds by <= k A 2^-24, so the sum of n members is off by <= A 2^-24 n^2 / 2 and the
-// side mean S~ / n (and likewise q~ / n in units of A^2) by <= n 2^-25 -- call it n 2^-24 with the rounding of the
-// differences themselves.  The fp32 path is held to 2e-5 of the field maximum; a tenth of that, 2e-6, allows
-// n <= 2e-6 x 2^24 = 33.  But the bound is in units of the eddy AMPLITUDE, and a flux mean is normalised by the
-// flux: with waves in quadrature (u' ~ sin 4 lon, v' ~ cos 4 lon, the fields of the test suite) max |u'v' mean| is
-// about A^2 / 10, and a part of a lat-lon row spans enough longitude for the whole wave to enter its sums.  Sides
-// of 32 measured 1.6e-5 ... 2.5e-5 of max |u'v' mean| on rows of 352 and 360 columns, sides of 8 -- the side of a
-// cubed sphere, whose members lie all around the globe -- 5e-6.  Hence parts of 8: n 2^-24 = 4.8e-7, forty times
-// under 2e-5 in units of A^2 and four times under it in the unit the results are compared in; two whole batches.
-// A side of up to TEMX_F32_SIDE_KEEP = 16 members is left whole: at the 1e-8 degrees of an fp32 plan five pairs of
-// neighbouring latitudes of ne240 fall into one class of 16 + 16, and the class tables of the cubed spheres that are
-// timed (ne30, ne120, ne240) stay as they were, bit for bit.
-#ifndef TEMX_F32_SIDE_CAP
-#define TEMX_F32_SIDE_CAP 8
-#endif
-#ifndef TEMX_F32_SIDE_KEEP
-#define TEMX_F32_SIDE_KEEP 16
-#endif
-
-static bool build_classes(const double* lat, int64_t N, ClassTables& ct, double tol_dflt, size_t side_cap = 0,
-                          size_t side_keep = 0) {
-  if (N >= ((int64_t)1 << 27) || N < 64) return false;     // row indices live in 27 bits of a table entry
-  const double tol = sym_tol_deg(tol_dflt);
-  std::vector<int> order((size_t)N);
-  for (int64_t i = 0; i < N; ++i) {
-    if (!(std::fabs(lat[i]) <= 90.0 + 1e-9)) return false;
-    order[(size_t)i] = (int)i;
-  }
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return std::fabs(lat[a]) < std::fabs(lat[b]); });
-  struct Cls {
-    double alat;
-    std::vector<int> n, s;
-  };
-  std::vector<Cls> cls;
-  for (size_t i = 0; i < order.size();) {
-    Cls c;
-    c.alat = std::fabs(lat[order[i]]);
-    size_t j = i;
-    for (; j < order.size() && std::fabs(lat[order[j]]) - c.alat <= tol; ++j) {
-      const int r = order[j];
-      (lat[r] < -tol ? c.s : c.n).push_back(r);      // equator columns count as northern
-    }
-    // the class sits at the mean |lat| of its members (they agree to within tol): deviations of either
-    // sign, half the size of those from the smallest member
-    long double sum = 0.0L;
-    for (size_t m = i; m < j; ++m) sum += (long double)std::fabs(lat[order[m]]) - (long double)c.alat;
-    c.alat += (double)(sum / (long double)(j - i));
-    std::sort(c.n.begin(), c.n.end());
-    std::sort(c.s.begin(), c.s.end());
-    cls.push_back(std::move(c));
-    i = j;
-  }
-  if ((double)N < 3.0 * (double)cls.size()) return false;   // < 3 columns per class: not worth it
-  constexpr int MB = CLS_MB;
-  auto nb = [](size_t m) { return (int)((m + MB - 1) / MB); };
-  // Outsized classes are cut into several classes at the same latitude.  Any subset of the columns of a
-  // latitude is a class (the algebra of kernels_cls.hpp holds per class side), and a class-group is the unit of
-  // work between two hand-overs of the shared-d-tile sweep and of the work cuts: the cubed sphere has ONE
-  // class of 1440 equator columns (360 batches) among 48 000 of 8 + 8 (4 batches), and every workgroup that
-  // met it ran 20 % longer -- all of them on one XCD (ne120 x 72 x 30, TEM + tracer sweep: 17.6 -> 14 ms).
-  {
-    std::map<std::pair<size_t, size_t>, size_t> hist;
-    for (const Cls& c : cls) ++hist[{c.n.size(), c.s.size()}];
-    std::pair<size_t, size_t> typ{0, 0};
-    size_t best = 0;
-    for (const auto& kv : hist)
-      if (kv.second > best) {
-        best = kv.second;
-        typ = kv.first;
-      }
-    const size_t cap_n = std::max<size_t>(typ.first, MB), cap_s = std::max<size_t>(typ.second, MB);
-    const int typ_b = std::max(1, nb(typ.first) + nb(typ.second));
-    std::vector<Cls> out;
-    out.reserve(cls.size());
-    for (Cls& c : cls) {
-      if (nb(c.n.size()) + nb(c.s.size()) <= 4 * typ_b) {
-        out.push_back(std::move(c));
-        continue;
-      }
-      const size_t parts = std::max((c.n.size() + cap_n - 1) / cap_n, (c.s.size() + cap_s - 1) / cap_s);
-      for (size_t k = 0; k < parts; ++k) {
-        Cls d;
-        d.alat = c.alat;
-        for (size_t m = k * cap_n; m < std::min((k + 1) * cap_n, c.n.size()); ++m) d.n.push_back(c.n[m]);
-        for (size_t m = k * cap_s; m < std::min((k + 1) * cap_s, c.s.size()); ++m) d.s.push_back(c.s[m]);
-        if (!d.n.empty() || !d.s.empty()) out.push_back(std::move(d));
-      }
-    }
-    cls.swap(out);
-  }
-  // fp32 plans: a side longer than side_keep members is cut into parts of side_cap (TEMX_F32_SIDE_CAP above).  A
-  // lat-lon, Gaussian or HEALPix-like grid has NLON members per side and NLON is the TYPICAL size there, so the cut
-  // above leaves them whole.  Each part is a class of its own at the same latitude, with its own first member as the
-  // origin of its sums.  Classes within side_keep -- every class of a cubed sphere from ne8 on, whose equator the cut
-  // above already took to 8 + 8 -- are not touched, and the order of the others among them is kept: a table without
-  // a long side comes out bit for bit as before.
-  if (side_cap) {
-    bool any = false;
-    for (const Cls& c : cls) any = any || c.n.size() > side_keep || c.s.size() > side_keep;
-    if (any) {
-      std::vector<Cls> out;
-      out.reserve(cls.size());
-      for (Cls& c : cls) {
-        if (c.n.size() <= side_keep && c.s.size() <= side_keep) {
-          out.push_back(std::move(c));
-          continue;
-        }
-        const size_t parts = (std::max(c.n.size(), c.s.size()) + side_cap - 1) / side_cap;
-        for (size_t k = 0; k < parts; ++k) {
-          Cls d;
-          d.alat = c.alat;
-          for (size_t m = k * side_cap; m < std::min((k + 1) * side_cap, c.n.size()); ++m) d.n.push_back(c.n[m]);
-          for (size_t m = k * side_cap; m < std::min((k + 1) * side_cap, c.s.size()); ++m) d.s.push_back(c.s[m]);
-          out.push_back(std::move(d));
-        }
-      }
-      cls.swap(out);
-    }
-  }
-  for (const Cls& c : cls) ct.max_side = std::max<int64_t>(ct.max_side, (int64_t)std::max(c.n.size(), c.s.size()));
-  // equal member counts inside a class-group; then by first row (some streaming order)
-  std::stable_sort(cls.begin(), cls.end(), [&](const Cls& a, const Cls& b) {
-    const int an = nb(a.n.size()), as = nb(a.s.size()), bn = nb(b.n.size()), bs = nb(b.s.size());
-    if (an != bn) return an > bn;
-    if (as != bs) return as > bs;
-    const int ar = a.n.empty() ? a.s[0] : a.n[0], br = b.n.empty() ? b.s[0] : b.n[0];
-    return ar < br;
-  });
-  // The class-groups (4 consecutive classes) of the few small strata -- ne240: 361 groups of 4 + 4 members and 90 of
-  // 8 + 0 behind 48 374 of 8 + 8 -- are spread evenly among the others: a work cut is a run of consecutive groups
-  // balanced by batch count, and the end of a group costs about as much as two batches, so the workgroup that got
-  // the tail of a size-sorted table ran 30 % longer than the rest (ne240 x 128 x 1: 1.9 instead of 1.5 ms;
-  // profiles/r03_lab20_class_order_d128_f32.log).  Inside a stratum the order stays.  A last, partial group stays last.
-  {
-    const size_t ngr = (cls.size() + 3) / 4;
-    std::vector<std::pair<int, int>> shape(ngr);
-    std::map<std::pair<int, int>, size_t> count, seen;
-    for (size_t gi = 0; gi < ngr; ++gi) {
-      int bN = 0, bS = 0;
-      for (size_t ci = gi * 4; ci < std::min(gi * 4 + 4, cls.size()); ++ci) {
-        bN = std::max(bN, nb(cls[ci].n.size()));
-        bS = std::max(bS, nb(cls[ci].s.size()));
-      }
-      shape[gi] = {bN, bS};
-      ++count[shape[gi]];
-    }
-    std::vector<std::pair<double, size_t>> key(ngr);
-    for (size_t gi = 0; gi < ngr; ++gi) {
-      const size_t i = seen[shape[gi]]++;
-      key[gi] = {((double)i + 0.5) / (double)count[shape[gi]], gi};
-      if (gi + 1 == ngr && cls.size() % 4 != 0) key[gi].first = 2.0;
-    }
-    std::stable_sort(key.begin(), key.end(), [](const std::pair<double, size_t>& a, const std::pair<double, size_t>& b) { return a.first < b.first; });
-    std::vector<Cls> out;
-    out.reserve(cls.size());
-    for (const auto& kv : key)
-      for (size_t ci = kv.second * 4; ci < std::min(kv.second * 4 + 4, cls.size()); ++ci) out.push_back(std::move(cls[ci]));
-    cls.swap(out);
-  }
-  ct.ncls = (int64_t)cls.size();
-  ct.ngroups = (ct.ncls + 3) / 4;
-  ct.xc.assign((size_t)(ct.ngroups + 1) * 4, 0.0);
-  ct.gbatch0.assign((size_t)ct.ngroups + 1, 0);
-  ct.cnt.assign((size_t)ct.ngroups * 8, 0.0);
-  ct.crow.clear();
-  const double d2r = M_PI / 180.0;
-  for (int64_t gi = 0; gi < ct.ngroups; ++gi) {
-    int bN = 0, bS = 0;
-    for (int k = 0; k < 4; ++k) {
-      const int64_t ci = gi * 4 + k;
-      if (ci >= ct.ncls) continue;
-      bN = std::max(bN, nb(cls[(size_t)ci].n.size()));
-      bS = std::max(bS, nb(cls[(size_t)ci].s.size()));
-      ct.xc[(size_t)ci] = std::cos((90.0 - cls[(size_t)ci].alat) * d2r);
-      ct.cnt[(size_t)gi * 8 + k] = (double)cls[(size_t)ci].n.size();
-      ct.cnt[(size_t)gi * 8 + 4 + k] = (double)cls[(size_t)ci].s.size();
-    }
-    ct.gbatch0[(size_t)gi] = (int)(ct.crow.size() / (4 * MB));
-    for (int side = 0; side < 2; ++side) {
-      const int nbat = side ? bS : bN;
-      for (int bi = 0; bi < nbat; ++bi) {
-        int flags = side ? CLS_SOUTH : 0;
-        if (bi == 0 && (side == 0 || bN == 0)) flags |= CLS_FIRST;
-        if (bi == nbat - 1 && (side == 1 || bS == 0)) flags |= CLS_LAST;
-        int batch[4 * MB];
-        bool haspad = false;
-        for (int k = 0; k < 4; ++k) {
-          const int64_t ci = gi * 4 + k;
-          for (int j = 0; j < MB; ++j) {
-            const size_t m = (size_t)bi * MB + j;
-            int ent = (int)0x80000000 | (flags << 28);
-            if (ci < ct.ncls) {
-              const std::vector<int>& mem = side ? cls[(size_t)ci].s : cls[(size_t)ci].n;
-              if (m < mem.size()) ent = mem[m] | (flags << 28);
-            }
-            haspad = haspad || ent < 0;
-            batch[k * MB + j] = ent;
-          }
-        }
-        for (int e = 0; e < 4 * MB; ++e) ct.crow.push_back(batch[e] | (haspad ? CLS_HASPAD_BIT : 0));
-      }
-    }
-  }
-  ct.nbatch = (int64_t)(ct.crow.size() / (4 * MB));
-  ct.gbatch0[(size_t)ct.ngroups] = (int)ct.nbatch;
-  ct.crow.resize(ct.crow.size() + (size_t)CLS_PADB * 4 * MB, (int)0x80000000);   // index loads run ahead
-  return true;
-}
-
-// (first batch, its group) of `nsub` pieces of the batch list: equal batch counts; a cut may fall
-// inside a class-group (the sweeps are linear in the member rows, the kernels project partial sums)
-#ifndef TEMX_GROUP_COST
-#define TEMX_GROUP_COST 2
-#endif
-static int class_cuts(temx_plan* pl, int nsub, const int2** out, bool group_aligned = false) {
+// work_cuts on the device, one buffer per (pieces, alignment): of the full table ...
+static int cached_cuts(std::map<int, DevBuf>& cache, const std::vector<int>& gbatch0, int64_t ngroups, int64_t nbatches,
+                       int nsub, bool group_aligned, const int2** out) {
   const int key = group_aligned ? -nsub : nsub;
-  auto it = pl->csplits.find(key);
-  if (it == pl->csplits.end()) {
-    std::vector<int> cut((size_t)2 * (nsub + 1));
-    int g = 0;
-    // group-aligned cuts balance batches + TEMX_GROUP_COST per class-group: the end of a group (exchange, reference,
-    // 100-160 MFMAs) costs about two batches, and the table ends with the small classes (ne240: 361 groups of 2
-    // batches), so that cuts by batch count alone gave the last workgroup twice the groups -- 1.9 instead of 1.5 ms
-    // for ne240 x 128 x 1 (profiles/r03_lab20_class_order_d128_f32.log)
-    const int64_t total = pl->cbatches + (int64_t)TEMX_GROUP_COST * pl->cgroups;
-    for (int k = 0; k <= nsub; ++k) {
-      const int64_t b = pl->cbatches * k / nsub;
-      if (group_aligned) {     // the one-pass sweep stores whole-class sums: cut at the next group boundary
-        const int64_t want = total * k / nsub;
-        while (g < pl->cgroups && pl->gbatch0[(size_t)g] + (int64_t)TEMX_GROUP_COST * g < want) ++g;
-        if (k == nsub) g = (int)pl->cgroups;
-        cut[(size_t)2 * k] = pl->gbatch0[(size_t)g];
-        cut[(size_t)2 * k + 1] = g;
-        continue;
-      }
-      while (g + 1 < pl->cgroups && pl->gbatch0[(size_t)g + 1] <= b) ++g;
-      cut[(size_t)2 * k] = (int)b;
-      cut[(size_t)2 * k + 1] = g;
-    }
+  auto it = cache.find(key);
+  if (it == cache.end()) {
     DevBuf b;
-    int rc = upload(b, cut.data(), cut.size() * sizeof(int));
-    if (rc) return rc;
-    it = pl->csplits.emplace(key, b).first;
+    if (int rc = upload(b, work_cuts(gbatch0, ngroups, nbatches, nsub, group_aligned))) return rc;
+    it = cache.emplace(key, b).first;
   }
   *out = static_cast<const int2*>(it->second.p);
   return TEMX_OK;
+}
+static int class_cuts_dev(temx_plan* pl, int nsub, const int2** out, bool group_aligned = false) {
+  return cached_cuts(pl->csplits, pl->gbatch0, pl->cgroups, pl->cbatches, nsub, group_aligned, out);
+}
+// ... and of the subsample of the single sweep's pre-pass (sub), always group-aligned
+static int os_cuts_dev(temx_plan* pl, bool sub, int nsub, const int2** out) {
+  if (!sub) return class_cuts_dev(pl, nsub, out, true);
+  return cached_cuts(pl->csplits_s, pl->sgbatch0, pl->sgroups, pl->sbatches, nsub, true, out);
 }
 
 #ifndef TEMX_CLS_E_WPS
@@ -980,7 +654,7 @@ template <typename T, int NF>
 static int launch_project_cls_t(temx_plan* pl, const FieldPtrs<NF>& fp, int64_t D, const double* colscale,
                                 int sfield, double* partial, const Split& sp, hipStream_t st) {
   const int2* cuts = nullptr;
-  if (int rc = class_cuts(pl, sp.nsplit, &cuts)) return rc;
+  if (int rc = class_cuts_dev(pl, sp.nsplit, &cuts)) return rc;
   dim3 grid(sp.grid), block(256);
 #define TEMX_LPC(TBSv, NFWv, WPSv, OPv)                                                             \
   hipLaunchKernelGGL((project_cls_kernel<T, NF, NFWv, TBSv, WPSv, cls_proj_pd<T>(OPv, NFWv), OPv>), grid, block, 0, st, fp, D, pl->K, \
@@ -1019,7 +693,7 @@ template <typename T, int KIND>
 static int launch_sweep_op_t(temx_plan* pl, const FieldPtrs<4>& fp, double* partial, const Split& sp, double* sums,
                              hipStream_t st) {
   const int2* cuts = nullptr;
-  if (int rc = class_cuts(pl, sp.nsplit, &cuts, true)) return rc;
+  if (int rc = class_cuts_dev(pl, sp.nsplit, &cuts, true)) return rc;
   dim3 grid(sp.grid), block(256);
   // the tracer sweep (42 accumulators) runs two waves per SIMD: a ring of 2 batches keeps it inside 256 registers
   constexpr int PDv = KIND == 1 ? (sizeof(T) == 4 ? 4 : 2) : (sizeof(T) == 4 ? TEMX_CLS_OP_PD_F32 : TEMX_CLS_OP_PD);
@@ -1055,7 +729,7 @@ static int launch_sweep_op_t(temx_plan* pl, const FieldPtrs<4>& fp, double* part
 template <typename T>
 static int launch_sweep_opw2_t(temx_plan* pl, const FieldPtrs<5>& fp, double* partial, const Split& sp, hipStream_t st) {
   const int2* cuts = nullptr;
-  if (int rc = class_cuts(pl, sp.nsplit * 4, &cuts, true)) return rc;
+  if (int rc = class_cuts_dev(pl, sp.nsplit * 4, &cuts, true)) return rc;
   dim3 grid(sp.grid), block(256);
   constexpr int PDv = sizeof(T) == 4 ? TEMX_CLS_OP_PD_F32 : TEMX_CLS_OP_PD;
 #define TEMX_LSW(TBSv)                                                                                       \
@@ -1087,7 +761,7 @@ template <typename T, int MODE, int DPW, int KIND>
 static int launch_eddy_cls_d(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
                              const Split& sp, const EddyOut& eo, hipStream_t st) {
   const int2* cuts = nullptr;
-  if (int rc = class_cuts(pl, sp.nsplit * (8 / DPW), &cuts)) return rc;
+  if (int rc = class_cuts_dev(pl, sp.nsplit * (8 / DPW), &cuts)) return rc;
   dim3 grid(sp.grid), block(512);
   constexpr int NFR = KIND == 0 ? 4 : 3;
 #define TEMX_LEC(TBSv)                                                                                \
@@ -1160,7 +834,7 @@ static int launch_flux_cls(temx_plan* pl, const double* C, double* partial, cons
 static int launch_class_sums(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, hipStream_t st) {
   const Split& sp = pl->sp_cproj4;
   const int2* cuts = nullptr;
-  if (int rc = class_cuts(pl, sp.nsplit, &cuts, true)) return rc;
+  if (int rc = class_cuts_dev(pl, sp.nsplit, &cuts, true)) return rc;
   dim3 grid(sp.grid), block(256);
 #define TEMX_LCS(Tv)                                                                                  \
   hipLaunchKernelGGL((project_cls_kernel<Tv, 4, 4, 2, TEMX_CLS_OP_WPS, cls_proj_pd<Tv>(true, 4), true, false>), grid, block, 0, st, \
@@ -1305,131 +979,6 @@ static int launch_eddy_sym_t(temx_plan* pl, const FieldPtrs<4>& fp, const double
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// host linear algebra: Cholesky inverse of the K x K Gram matrix (K <= 64)
-// ------------------------------------------------------------------------------------------------
-// Li = L^-1 for G = L L^T (long double); -1 when G is not numerically positive definite
-static int spd_factor(const double* G, int K, std::vector<long double>& Li) {
-  std::vector<long double> Lm((size_t)K * K, 0.0L);
-  Li.assign((size_t)K * K, 0.0L);
-  for (int i = 0; i < K; ++i) {
-    for (int j = 0; j <= i; ++j) {
-      long double s = G[i * K + j];
-      for (int k = 0; k < j; ++k) s -= Lm[i * K + k] * Lm[j * K + k];
-      if (i == j) {
-        if (!(s > 0.0L) || !(s <= 1e300L)) return -1;
-        Lm[i * K + i] = sqrtl(s);
-      } else {
-        Lm[i * K + j] = s / Lm[j * K + j];
-      }
-    }
-  }
-  // a rank-deficient Gram shows up as a tiny pivot relative to the diagonal
-  for (int i = 0; i < K; ++i)
-    if (Lm[i * K + i] * Lm[i * K + i] < 1e-13L * (long double)G[i * K + i]) return -1;
-  for (int c = 0; c < K; ++c) {  // Li = L^-1 by forward substitution
-    for (int i = c; i < K; ++i) {
-      long double s = (i == c) ? 1.0L : 0.0L;
-      for (int k = c; k < i; ++k) s -= Lm[i * K + k] * Li[k * K + c];
-      Li[i * K + c] = s / Lm[i * K + i];
-    }
-  }
-  return 0;
-}
-
-// G^-1 = L^-T L^-1
-static void inverse_from_factor(const std::vector<long double>& Li, int K, double* Ginv) {
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) {
-      long double s = 0.0L;
-      for (int k = std::max(i, j); k < K; ++k) s += Li[k * K + i] * Li[k * K + j];
-      Ginv[i * K + j] = (double)s;
-    }
-}
-
-// Pseudo-inverse of the symmetric positive semi-definite Gram matrix by cyclic Jacobi rotations
-// (K <= 64).  Used when Cholesky fails: pinv(Y0) = pinv(G) Y0^T holds for any rank, which is the
-// minimum-norm semantics of the reference's lstsq (gelsd) for a rank-deficient Y0 -- fewer distinct
-// latitudes than harmonics.  Eigenvalues below 1e-12 * lambda_max are treated as zero.
-static int sym_pinv(const double* G, int K, double* Ginv, int* rank_out) {
-  std::vector<long double> A((size_t)K * K), V((size_t)K * K, 0.0L);
-  for (int i = 0; i < K * K; ++i) A[i] = G[i];
-  for (int i = 0; i < K; ++i) V[(size_t)i * K + i] = 1.0L;
-  for (int sweep = 0; sweep < 100; ++sweep) {
-    long double off = 0.0L, diag = 0.0L;
-    for (int i = 0; i < K; ++i)
-      for (int j = 0; j < K; ++j) (i == j ? diag : off) += A[(size_t)i * K + j] * A[(size_t)i * K + j];
-    if (off <= 1e-60L * diag) break;
-    for (int p = 0; p < K - 1; ++p)
-      for (int q = p + 1; q < K; ++q) {
-        const long double apq = A[(size_t)p * K + q];
-        if (apq == 0.0L) continue;
-        const long double theta = (A[(size_t)q * K + q] - A[(size_t)p * K + p]) / (2.0L * apq);
-        const long double t = (theta >= 0 ? 1.0L : -1.0L) / (fabsl(theta) + sqrtl(theta * theta + 1.0L));
-        const long double c = 1.0L / sqrtl(t * t + 1.0L), sn = t * c;
-        for (int k = 0; k < K; ++k) {   // A <- A J
-          const long double akp = A[(size_t)k * K + p], akq = A[(size_t)k * K + q];
-          A[(size_t)k * K + p] = c * akp - sn * akq;
-          A[(size_t)k * K + q] = sn * akp + c * akq;
-        }
-        for (int k = 0; k < K; ++k) {   // A <- J^T A
-          const long double apk = A[(size_t)p * K + k], aqk = A[(size_t)q * K + k];
-          A[(size_t)p * K + k] = c * apk - sn * aqk;
-          A[(size_t)q * K + k] = sn * apk + c * aqk;
-        }
-        for (int k = 0; k < K; ++k) {   // V <- V J
-          const long double vkp = V[(size_t)k * K + p], vkq = V[(size_t)k * K + q];
-          V[(size_t)k * K + p] = c * vkp - sn * vkq;
-          V[(size_t)k * K + q] = sn * vkp + c * vkq;
-        }
-      }
-  }
-  long double lmax = 0.0L;
-  for (int i = 0; i < K; ++i) lmax = std::max(lmax, A[(size_t)i * K + i]);
-  if (!(lmax > 0.0L)) return -1;
-  int rank = 0;
-  std::vector<long double> inv(K, 0.0L);
-  for (int i = 0; i < K; ++i)
-    if (A[(size_t)i * K + i] > 1e-12L * lmax) {
-      inv[i] = 1.0L / A[(size_t)i * K + i];
-      ++rank;
-    }
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) {
-      long double s2 = 0.0L;
-      for (int k = 0; k < K; ++k) s2 += V[(size_t)i * K + k] * inv[k] * V[(size_t)j * K + k];
-      Ginv[(size_t)i * K + j] = (double)s2;
-    }
-  *rank_out = rank;
-  return 0;
-}
-
-// np.gradient(f, x) coefficient table out[i] = a f[i-1] + b f[i] + c f[i+1], edge_order = 1
-// (tem_util.py:154, 192).  numpy switches to the uniform formula only when diff(x) is bit-uniform.
-static void gradient_table(const std::vector<double>& x, std::vector<double>& tab) {
-  const int n = (int)x.size();
-  tab.assign((size_t)n * 3, 0.0);
-  std::vector<double> dx(n - 1);
-  for (int i = 0; i + 1 < n; ++i) dx[i] = x[i + 1] - x[i];
-  bool uniform = true;
-  for (int i = 1; i + 1 < n; ++i) uniform = uniform && (dx[i] == dx[0]);
-  for (int i = 1; i + 1 < n; ++i) {
-    if (uniform) {
-      tab[i * 3 + 0] = -1.0 / (2.0 * dx[0]);
-      tab[i * 3 + 2] = 1.0 / (2.0 * dx[0]);
-    } else {
-      const double d1 = dx[i - 1], d2 = dx[i];
-      tab[i * 3 + 0] = -(d2) / (d1 * (d1 + d2));
-      tab[i * 3 + 1] = (d2 - d1) / (d1 * d2);
-      tab[i * 3 + 2] = d1 / (d2 * (d1 + d2));
-    }
-  }
-  tab[0 * 3 + 1] = -1.0 / dx[0];
-  tab[0 * 3 + 2] = 1.0 / dx[0];
-  tab[(n - 1) * 3 + 0] = -1.0 / dx[n - 2];
-  tab[(n - 1) * 3 + 1] = 1.0 / dx[n - 2];
-}
-
 // The fused second sweep reads ONE set of Y0 blocks for the reconstruction and for the projection, so it
 // serves neither K > 64 nor weights mode (projection rows scaled by 4 pi w, reconstruction rows not).
 static inline bool unfused_stage2(const temx_plan* pl) { return pl->large || pl->weighted; }
@@ -1494,73 +1043,6 @@ static FieldPtrs<4> four(const void* a, const void* b, const void* c, const void
 // (tools/proto/single_sweep_numerics.py).  Used by temx_tem_run only (the staged, all-reducible stages keep the
 // class-sum path).
 
-// Gauss-Legendre nodes and weights on [-1, 1] (long double, Newton on P_n)
-static void gauss_legendre(int n, std::vector<long double>& x, std::vector<long double>& w) {
-  x.assign(n, 0.0L);
-  w.assign(n, 0.0L);
-  const long double pi = 3.141592653589793238462643383279502884L;
-  for (int i = 0; i < (n + 1) / 2; ++i) {
-    long double z = cosl(pi * (i + 0.75L) / (n + 0.5L)), pp = 0.0L;
-    for (int it = 0; it < 100; ++it) {
-      long double p1 = 1.0L, p2 = 0.0L;
-      for (int j = 1; j <= n; ++j) {
-        const long double p3 = p2;
-        p2 = p1;
-        p1 = ((2.0L * j - 1.0L) * z * p2 - (j - 1.0L) * p3) / j;
-      }
-      pp = n * (z * p1 - p2) / (z * z - 1.0L);
-      const long double dz = p1 / pp;
-      z -= dz;
-      if (fabsl(dz) < 1e-19L) break;
-    }
-    x[i] = -z;
-    x[n - 1 - i] = z;
-    w[i] = w[n - 1 - i] = 2.0L / ((1.0L - z * z) * pp * pp);
-  }
-}
-
-// normalised Y_l^0 at x = cos(colat), l < n (long double)
-static void ylm0_row(long double xv, int n, long double* y) {
-  const long double pi = 3.141592653589793238462643383279502884L;
-  long double pm1 = 1.0L, pc = xv;
-  for (int l = 0; l < n; ++l) {
-    long double P;
-    if (l == 0) {
-      P = 1.0L;
-    } else if (l == 1) {
-      P = xv;
-    } else {
-      const long double pn = ((2 * l - 1) * xv * pc - (l - 1) * pm1) / l;
-      pm1 = pc;
-      pc = pn;
-      P = pn;
-    }
-    y[l] = sqrtl((2.0L * l + 1.0L) / (4.0L * pi)) * P;
-  }
-}
-
-static int os_cuts(temx_plan* pl, bool sub, int nsub, const int2** out) {
-  if (!sub) return class_cuts(pl, nsub, out, true);
-  auto it = pl->csplits_s.find(nsub);
-  if (it == pl->csplits_s.end()) {
-    std::vector<int> cut((size_t)2 * (nsub + 1));
-    int g = 0;
-    const int64_t total = pl->sbatches + (int64_t)TEMX_GROUP_COST * pl->sgroups;     // as class_cuts
-    for (int k = 0; k <= nsub; ++k) {
-      const int64_t want = total * k / nsub;
-      while (g < pl->sgroups && pl->sgbatch0[(size_t)g] + (int64_t)TEMX_GROUP_COST * g < want) ++g;
-      if (k == nsub) g = (int)pl->sgroups;
-      cut[(size_t)2 * k] = pl->sgbatch0[(size_t)g];
-      cut[(size_t)2 * k + 1] = g;
-    }
-    DevBuf b;
-    if (int rc = upload(b, cut.data(), cut.size() * sizeof(int))) return rc;
-    it = pl->csplits_s.emplace(nsub, b).first;
-  }
-  *out = static_cast<const int2*>(it->second.p);
-  return TEMX_OK;
-}
-
 // tables that depend on the grid and L only (built once per plan, at the first eligible temx_plan_set_tem)
 static int build_os_tables(temx_plan* pl) {
   if (pl->os_built) return TEMX_OK;
@@ -1572,174 +1054,75 @@ static int build_os_tables(temx_plan* pl) {
   pl->TBX = TBX;
   pl->KR = KR;
   int rc;
-  // basis up to degree 2L at the class latitudes, Y basis (no re-orthogonalisation: these are raw projections)
+  // subsample of class-groups for the reference fit (TEMX_OPT_OS_SUBSAMPLE / env TEMX_OS_SUBSAMPLE: groups kept)
+  const char* ess = getenv("TEMX_OS_SUBSAMPLE");
+  const ClassSubsample ss = class_subsample(pl->h_crow, pl->h_xc, pl->gbatch0, pl->cgroups, ess ? std::max(4, atoi(ess)) : pl->os_keep);
+  pl->sgbatch0 = ss.gbatch0;
+  pl->sgroups = ss.ngroups;
+  pl->sbatches = ss.nbatch;
+  if ((rc = upload(pl->crow_s, ss.crow))) return rc;
+  // one row table per side, for the full table and for the subsample (sweep_os2_kernel: a wave per class side)
+  for (int sub = 0; sub < 2; ++sub) {
+    SideTables stb;
+    if (sub) build_side_tables(ss.crow, ss.gbatch0, ss.ngroups, stb);
+    else build_side_tables(pl->h_crow, pl->gbatch0, pl->cgroups, stb);
+    for (int sd = 0; sd < 2; ++sd) {
+      if ((rc = upload(pl->side_crow[sub][sd], stb.crow[sd]))) return rc;
+      if ((rc = upload(pl->side_gfirst[sub][sd], stb.gfirst[sd]))) return rc;
+    }
+  }
+  // basis up to degree 2L at the class latitudes of the full table and of the subsample, Y basis (no
+  // re-orthogonalisation: these are raw projections)
   {
     std::vector<double> nx((size_t)8 * TBX + 8, 0.0);
     for (int l = 0; l < KX; ++l) nx[(size_t)l] = std::sqrt((2.0 * l + 1.0) / (4.0 * M_PI));
-    DevBuf nd;
-    if ((rc = upload(nd, nx.data(), nx.size() * 8))) return rc;
-    rc = pl->ycx.ensure((size_t)(pl->cgroups + 1) * 2 * TBX * 16 * 8);
-    if (!rc) {
+    DevBuf nd, xs;
+    if (!(rc = upload(nd, nx)) && !(rc = upload(xs, ss.xc)) && !(rc = pl->ycx.ensure((size_t)(pl->cgroups + 1) * 2 * TBX * 16 * 8)) &&
+        !(rc = pl->ycx_s.ensure((size_t)(pl->sgroups + 1) * 2 * TBX * 16 * 8))) {
       hipLaunchKernelGGL(cls_basis_kernel<512>, dim3((unsigned)((pl->cls_npad + 255) / 256)), dim3(256), 0, 0, pl->xc.d(),
                          pl->ncls, pl->cls_npad, KX, TBX, nd.d(), (const double*)nullptr, pl->ycx.d());
-      // subsample of class-groups for the reference fit: every S-th group, its batches copied
-      // (32 class-groups = 128 latitudes for the 16 coefficients of a column -- the fit only has to be decent, it is
-      // removed again exactly; 96 groups cost 0.15 instead of 0.06 ms at ne120 x 72 x 30 and 0.5 instead of 0.2 ms at
-      // ne30 x 72 x 91.  TEMX_OPT_OS_SUBSAMPLE / env TEMX_OS_SUBSAMPLE: groups kept)
-      const char* ess = getenv("TEMX_OS_SUBSAMPLE");
-      const int64_t keep = ess ? std::max(4, atoi(ess)) : pl->os_keep;
-      const int64_t S = std::max<int64_t>(1, std::min<int64_t>(256, pl->cgroups / keep));
-      std::vector<int> crow_s;
-      std::vector<double> xc_s;
-      pl->sgbatch0.clear();
-      for (int64_t gi = 0; gi < pl->cgroups; gi += S) {
-        pl->sgbatch0.push_back((int)(crow_s.size() / (4 * CLS_MB)));
-        const size_t e0 = (size_t)pl->gbatch0[(size_t)gi] * 4 * CLS_MB, e1 = (size_t)pl->gbatch0[(size_t)gi + 1] * 4 * CLS_MB;
-        crow_s.insert(crow_s.end(), pl->h_crow.begin() + e0, pl->h_crow.begin() + e1);
-        for (int k = 0; k < 4; ++k) xc_s.push_back(pl->h_xc[(size_t)gi * 4 + k]);
-      }
-      pl->sgroups = (int64_t)pl->sgbatch0.size();
-      pl->sbatches = (int64_t)(crow_s.size() / (4 * CLS_MB));
-      pl->sgbatch0.push_back((int)pl->sbatches);
-      {   // one row table per side, for the full table and for the subsample (sweep_os2_kernel: a wave per class side)
-        SideTables stb;
-        build_side_tables(pl->h_crow, pl->gbatch0, pl->cgroups, CLS_MB, CLS_PADB, CLS_SOUTH, CLS_FIRST, CLS_LAST, CLS_HASPAD_BIT, stb);
-        for (int sd = 0; sd < 2 && !rc; ++sd)
-          if (!(rc = upload(pl->side_crow[0][sd], stb.crow[sd].data(), stb.crow[sd].size() * sizeof(int))))
-            rc = upload(pl->side_gfirst[0][sd], stb.gfirst[sd].data(), stb.gfirst[sd].size() * sizeof(int));
-        std::vector<int> crow_full = crow_s;      // (not yet padded) + the terminating entry of sgbatch0
-        build_side_tables(crow_full, pl->sgbatch0, pl->sgroups, CLS_MB, CLS_PADB, CLS_SOUTH, CLS_FIRST, CLS_LAST, CLS_HASPAD_BIT, stb);
-        for (int sd = 0; sd < 2 && !rc; ++sd)
-          if (!(rc = upload(pl->side_crow[1][sd], stb.crow[sd].data(), stb.crow[sd].size() * sizeof(int))))
-            rc = upload(pl->side_gfirst[1][sd], stb.gfirst[sd].data(), stb.gfirst[sd].size() * sizeof(int));
-      }
-      crow_s.resize(crow_s.size() + (size_t)CLS_PADB * 4 * CLS_MB, (int)0x80000000);
-      xc_s.resize(xc_s.size() + 4, 0.0);
-      DevBuf xs;
-      if (!rc && !(rc = upload(pl->crow_s, crow_s.data(), crow_s.size() * sizeof(int))) && !(rc = upload(xs, xc_s.data(), xc_s.size() * 8)) &&
-          !(rc = pl->ycx_s.ensure((size_t)(pl->sgroups + 1) * 2 * TBX * 16 * 8))) {
-        const int64_t np = (pl->sgroups + 1) * 4;
-        // classes beyond the real ones in the last group of the full table have count 0 and x = 0: harmless rows
-        hipLaunchKernelGGL(cls_basis_kernel<512>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, xs.d(), pl->sgroups * 4,
-                           np, KX, TBX, nd.d(), (const double*)nullptr, pl->ycx_s.d());
-      }
-      hipError_t e = hipDeviceSynchronize();
-      xs.release();
-      if (!rc && e != hipSuccess) rc = fail(TEMX_EHIP, "extended class basis failed: %s", hipGetErrorString(e));
-      // Gram matrix of the subsample, degree < KR, and its inverse
-      if (!rc) {
-        std::vector<long double> y((size_t)KR);
-        std::vector<double> Gs((size_t)KR * KR, 0.0);
-        std::vector<long double> Gl((size_t)KR * KR, 0.0L);
-        for (int64_t gi = 0; gi < pl->cgroups; gi += S)   // (the same groups as above)
-          for (int k = 0; k < 4; ++k) {
-            const long double nN = pl->h_cnt[(size_t)gi * 8 + k], nS = pl->h_cnt[(size_t)gi * 8 + 4 + k];
-            if (nN + nS == 0.0L) continue;
-            ylm0_row((long double)pl->h_xc[(size_t)gi * 4 + k], KR, y.data());
-            for (int l = 0; l < KR; ++l)
-              for (int m = 0; m < KR; ++m) Gl[(size_t)l * KR + m] += (nN + (((l + m) & 1) ? -nS : nS)) * y[l] * y[m];
-          }
-        for (size_t i = 0; i < Gs.size(); ++i) Gs[i] = (double)Gl[i];
-        pl->h_Gs = Gs;
-        std::vector<long double> Li;
-        std::vector<double> Gi((size_t)KR * KR);
-        if (spd_factor(Gs.data(), KR, Li) != 0) {
-          // A rank of an ncol-sharded job owns a band of latitudes, which need not determine the fit on its own:
-          // the job's subsample is the union over the ranks, its Gram matrix comes through
-          // temx_plan_set_os_matrices (the sweeps refuse to run before that).
-          if (pl->ext_G) {
-            pl->os_need_global = true;
-            std::fill(Gi.begin(), Gi.end(), 0.0);
-            rc = upload(pl->Gsinv, Gi.data(), Gi.size() * 8);
-          } else {
-            rc = fail(TEMX_ERANK, "the subsample of latitude classes does not determine a degree-%d reference", KR - 1);
-          }
-        } else {
-          inverse_from_factor(Li, KR, Gi.data());
-          rc = upload(pl->Gsinv, Gi.data(), Gi.size() * 8);
-        }
-      }
+      const int64_t np = (pl->sgroups + 1) * 4;
+      hipLaunchKernelGGL(cls_basis_kernel<512>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, xs.d(), pl->sgroups * 4,
+                         np, KX, TBX, nd.d(), (const double*)nullptr, pl->ycx_s.d());
+      const hipError_t e = hipDeviceSynchronize();
+      if (e != hipSuccess) rc = fail(TEMX_EHIP, "extended class basis failed: %s", hipGetErrorString(e));
     }
     nd.release();
+    xs.release();
     if (rc) return rc;
+  }
+  // Gram matrix of the subsample, degree < KR, and its inverse
+  {
+    pl->h_Gs = subsample_gram(pl->h_xc, pl->h_cnt, pl->cgroups, ss.S, KR);
+    std::vector<long double> Li;
+    std::vector<double> Gi((size_t)KR * KR, 0.0);
+    if (spd_factor(pl->h_Gs.data(), KR, Li) == 0) {
+      inverse_from_factor(Li, KR, Gi.data());
+    } else if (pl->ext_G) {
+      // A rank of an ncol-sharded job owns a band of latitudes, which need not determine the fit on its own:
+      // the job's subsample is the union over the ranks, its Gram matrix comes through
+      // temx_plan_set_os_matrices (the sweeps refuse to run before that).
+      pl->os_need_global = true;
+    } else {
+      return fail(TEMX_ERANK, "the subsample of latitude classes does not determine a degree-%d reference", KR - 1);
+    }
+    if ((rc = upload(pl->Gsinv, Gi))) return rc;
   }
   // Gauss-Legendre nodes for the transform form of the product linearisation (exact for degree 4L)
   {
     const int nq = 2 * L + 2;
     pl->NQ = nq;
-    std::vector<long double> xq, wq;
-    gauss_legendre(nq, xq, wq);
-    std::vector<long double> row((size_t)KX);
-    std::vector<double> Yq((size_t)nq * KX), w2((size_t)nq);
-    const long double twopi = 2.0L * 3.141592653589793238462643383279502884L;
-    for (int q = 0; q < nq; ++q) {
-      ylm0_row(xq[(size_t)q], KX, row.data());
-      for (int k = 0; k < KX; ++k) Yq[(size_t)q * KX + k] = (double)row[(size_t)k];
-      w2[(size_t)q] = (double)(twopi * wq[(size_t)q]);
-    }
-    if ((rc = upload(pl->gaunt, Yq.data(), Yq.size() * 8))) return rc;       // (Yq[q][k])
-    pl->h_Yq = Yq;
-    if ((rc = upload(pl->wq2, w2.data(), w2.size() * 8))) return rc;
+    const QuadBasis qb = quadrature_basis(nq, KX);
+    pl->h_Yq.assign(qb.Y.begin(), qb.Y.end());                              // (Yq[q][k])
+    if ((rc = upload(pl->gaunt, pl->h_Yq))) return rc;
+    if ((rc = upload(pl->wq2, std::vector<double>(qb.w2.begin(), qb.w2.end())))) return rc;
   }
   // Gx[l][k] = sum over the native columns of Y_l Y_k, l < K, k < KX (per latitude class; host threads)
-  {
-    const int nth = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<std::vector<double>> part((size_t)nth, std::vector<double>((size_t)K * KX, 0.0));
-    std::vector<std::thread> th;
-    auto stripe = [&](int t) {
-        std::vector<double> yy((size_t)KX);
-        std::vector<long double> y((size_t)KX);
-        std::vector<double>& Gp = part[(size_t)t];
-        for (int64_t ci = t; ci < pl->ncls; ci += nth) {
-          const int64_t gi = ci >> 2;
-          const int k4 = (int)(ci & 3);
-          const double nN = pl->h_cnt[(size_t)gi * 8 + k4], nS = pl->h_cnt[(size_t)gi * 8 + 4 + k4];
-          ylm0_row((long double)pl->h_xc[(size_t)ci], KX, y.data());
-          for (int k = 0; k < KX; ++k) yy[(size_t)k] = (double)y[(size_t)k];
-          const double se = nN + nS, so = nN - nS;
-          for (int l = 0; l < K; ++l) {
-            const double yl = yy[(size_t)l];
-            double* row = &Gp[(size_t)l * KX];
-            for (int k = (l & 1); k < KX; k += 2) row[k] += se * yl * yy[(size_t)k];        // l + k even
-            for (int k = 1 - (l & 1); k < KX; k += 2) row[k] += so * yl * yy[(size_t)k];    // l + k odd
-          }
-        }
-    };
-    // stripe t of the classes per thread; a thread that cannot be started (std::system_error under a process /
-    // thread limit -- this is an extern "C" call chain, nothing may propagate) leaves its stripe to the caller.
-    // The partial sums stay per stripe, so the result has the same bits however the stripes were run.
-    int started = 0;
-    try {
-      th.reserve((size_t)nth);
-      for (; started < nth - 1; ++started) th.emplace_back(stripe, started);
-    } catch (...) {
-    }
-    for (int t = started; t < nth; ++t) stripe(t);
-    for (auto& x : th) x.join();
-    std::vector<double> Gx((size_t)K * KX, 0.0);
-    for (int t = 0; t < nth; ++t)          // fixed order: the same bits whatever the scheduling
-      for (size_t i = 0; i < Gx.size(); ++i) Gx[i] += part[(size_t)t][i];
-    if ((rc = upload(pl->Gx, Gx.data(), Gx.size() * 8))) return rc;
-    pl->h_Gx_own = Gx;
-    pl->h_Gx = std::move(Gx);
-  }
+  pl->h_Gx = extended_gram(pl->h_xc, pl->h_cnt, pl->ncls, K, KX, (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+  pl->h_Gx_own = pl->h_Gx;
+  if ((rc = upload(pl->Gx, pl->h_Gx))) return rc;
   pl->os_built = true;
   return os_upload_blocks(pl);
-}
-
-// 16 x 4 A-operand blocks (kernels_osc.hpp) of the R x C matrix A (row-major, leading dimension ld): nrb4 blocks of 4
-// rows are padded to whole 16-row blocks, the columns to nkb blocks of 4; zero filled; appended to `out`
-static void append_blocks16(std::vector<double>& out, const double* A, int R, int C, int ld, bool transpose, int nrb4, int nkb) {
-  const size_t o = out.size();
-  const int nrb = (nrb4 + 3) / 4;
-  out.resize(o + (size_t)nrb * nkb * 64, 0.0);
-  for (int rb = 0; rb < nrb; ++rb)
-    for (int t = 0; t < nkb; ++t)
-      for (int k = 0; k < 4; ++k)
-        for (int m = 0; m < 16; ++m) {
-          const int r = 16 * rb + m, c = 4 * t + k;         // element [r][c] of the (transposed) matrix
-          if (r < R && c < C) out[o + ((size_t)rb * nkb + t) * 64 + k * 16 + m] = transpose ? A[(size_t)c * ld + r] : A[(size_t)r * ld + c];
-        }
 }
 
 // the matrices of the single sweep's contraction as MFMA operand blocks: after build_os_tables, and again whenever
@@ -1777,7 +1160,7 @@ static int launch_sweep_os_t(temx_plan* pl, const FieldPtrs<4>& fp, bool sub, co
                              const Split& sp, hipStream_t st) {
   using KD = OsKind<KIND>;
   const int2* cuts = nullptr;
-  if (int rc = os_cuts(pl, sub, sp.nsplit, &cuts)) return rc;
+  if (int rc = os_cuts_dev(pl, sub, sp.nsplit, &cuts)) return rc;
   dim3 grid(sp.grid), block(256);
   constexpr int NBR = 2;
   constexpr int PDv = sizeof(T) == 4 ? 4 : 2;       // (a 3-deep ring measured slower for the tracer kind: 8.7 vs 8.4 ms)
@@ -2267,29 +1650,6 @@ static int vert_tables(int device, const std::vector<double>& host, const double
   return TEMX_OK;
 }
 
-// The slab-staged map: how many columns a workgroup takes and how their walks are cut, from an LDS budget of 48 KiB
-// (three workgroups per CU: one loads while another walks).  false: one column does not fit (long rows).
-static bool vert_slab_shape(int nf, int nlev, int64_t nt, int nplev, size_t tsz, size_t psz, VertSlab* sh, size_t* lds) {
-  if (nt > VERT_THREADS / 4) return false;
-  const int colsz = nlev * (int)nt, ocolsz = nplev * (int)nt;
-  sh->in_stride = colsz | 1;
-  sh->out_stride = ocolsz | 1;
-  const size_t percol = (size_t)nf * (sh->in_stride + sh->out_stride) * tsz + (size_t)sh->in_stride * psz;
-  const size_t budget = 48 * 1024 - VERT_THREADS * sizeof(int) - (2 * nf + 1) * 16;
-  int cw = (int)std::min<size_t>(budget / percol, (size_t)(VERT_THREADS / nt));
-  if (cw < 1) return false;
-  sh->cw = cw;
-  const int pairs = cw * (int)nt, brackets = nlev - 1, most = VERT_THREADS / pairs;
-  sh->seg = std::max(4, (brackets + most - 1) / most);
-  sh->nseg = (brackets + sh->seg - 1) / sh->seg;
-  auto r16 = [](size_t b) { return (int)((b + 15) & ~(size_t)15); };
-  sh->in_img = r16((size_t)cw * sh->in_stride * tsz);
-  sh->out_img = r16((size_t)cw * sh->out_stride * tsz);
-  sh->p_img = r16((size_t)cw * sh->in_stride * psz);
-  *lds = VERT_THREADS * sizeof(int) + sh->p_img + (size_t)nf * (sh->in_img + sh->out_img);
-  return true;
-}
-
 template <typename T, int NF, bool HYB>
 static int launch_vert(const VertPtrs<NF>& fp, int nf, int64_t ncol, int nlev, int64_t nt, int nplev, const VertTab& tb,
                        double p0, const void* P, int p_f32, int logp, int hold, int map, hipStream_t st) {
@@ -2325,32 +1685,6 @@ static int launch_vert_nf(int nf, const void* const* src, void* const* dst, int6
   VertPtrs<VERT_NFMAX> fp{};
   for (int f = 0; f < nf; ++f) fp.src[f] = src[f], fp.dst[f] = dst[f];
   return launch_vert<T, VERT_NFMAX, HYB>(fp, nf, ncol, nlev, nt, nplev, tb, p0, P, p_f32, logp, hold, map, st);
-}
-
-// ---- re-layout: tile of a launch (kernels_layout.hpp) -----------------------------------------------------------
-// rmax rows of 64 columns fill the 32 KiB tile.  A window of ntb <= rmax times moves whole, with as many levels per
-// tile as fit (the run a column writes is kl * ntb elements); up to 2 rmax it still moves whole, over 32 columns;
-// a longer one is cut into chunks of rmax times, one level per tile.
-static LayoutTile layout_tile(int64_t ncol, int nlev, int64_t ntb, size_t dsz) {
-  LayoutTile tl{};
-  const int rmax = (int)(32 * 1024 / (64 * dsz));
-  tl.tc_shift = 6;
-  if (ntb <= rmax) {
-    tl.tt = (int)ntb;
-    tl.kl = std::max(1, std::min(nlev, rmax / (int)ntb));
-  } else if (ntb <= 2 * rmax) {
-    tl.tc_shift = 5;
-    tl.tt = (int)ntb;
-    tl.kl = 1;
-  } else {
-    tl.tt = rmax;
-    tl.kl = 1;
-  }
-  tl.stride = (tl.kl * tl.tt) | 1;
-  tl.nct = (int)((ncol + (1 << tl.tc_shift) - 1) >> tl.tc_shift);
-  tl.nlt = (nlev + tl.kl - 1) / tl.kl;
-  tl.ntt = (int)((ntb + tl.tt - 1) / tl.tt);
-  return tl;
 }
 
 extern "C" {
@@ -2428,7 +1762,7 @@ static int build_out_basis(temx_plan* pl, const double* T, double* dst, bool blo
   if (blocks && pl->K <= 64) {   // blocked copy for solve_mfma_kernel
     std::vector<double> yp((size_t)pl->M * pl->K);
     HIPCHK(hipMemcpy(yp.data(), dst, yp.size() * 8, hipMemcpyDeviceToHost));
-    return upload_blocks(pl->ypblk, yp.data(), pl->M, pl->K, pl->TB);
+    return upload(pl->ypblk, pack_blocks4(yp.data(), pl->M, pl->K, pl->TB));
   }
   return TEMX_OK;
 }
@@ -2560,7 +1894,7 @@ int temx_plan_create(temx_plan** out, int device, int64_t ncol, int L, int M,
     ClassTables ct;
     if ((!pl->large || pl->K <= 256) && !(flags & (TEMX_NO_SYMMETRY | TEMX_NO_CLASSES)) && !(e0 && e0[0] == '1') &&
         !(e1 && e1[0] == '1') &&
-        build_classes(lat_deg_host, ncol, ct, tol_dflt, (flags & TEMX_LAT_TOL_F32) ? (size_t)TEMX_F32_SIDE_CAP : 0, TEMX_F32_SIDE_KEEP)) {
+        build_classes(lat_deg_host, ncol, ct, sym_tol_deg(tol_dflt), (flags & TEMX_LAT_TOL_F32) ? (size_t)TEMX_F32_SIDE_CAP : 0, TEMX_F32_SIDE_KEEP)) {
       if ((rc = upload(pl->crow, ct.crow.data(), ct.crow.size() * sizeof(int)))) return bail(rc);
 
       if ((rc = upload(pl->ccnt, ct.cnt.data(), ct.cnt.size() * 8))) return bail(rc);
@@ -2602,7 +1936,7 @@ int temx_plan_create(temx_plan** out, int device, int64_t ncol, int L, int M,
   if (!pl->cls) {
     const char* e = getenv("TEMX_NO_SYM");
     std::vector<int> rN, rS;
-    if (!pl->large && !(flags & TEMX_NO_SYMMETRY) && !(e && e[0] == '1') && find_mirror_pairs(lat_deg_host, ncol, rN, rS, tol_dflt)) {
+    if (!pl->large && !(flags & TEMX_NO_SYMMETRY) && !(e && e[0] == '1') && find_mirror_pairs(lat_deg_host, ncol, rN, rS, sym_tol_deg(tol_dflt))) {
       pl->npair = (int64_t)rN.size();
       pl->npg = (pl->npair + 3) / 4;
       pl->npg_alloc = ((pl->npg + SYM_PROJ_CH - 1) / SYM_PROJ_CH + 1) * SYM_PROJ_CH;   // whole chunks + 1 chunk
@@ -3051,7 +2385,7 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
   if ((int64_t)nlev * nt >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "nlev*nt must be < 2^28");
   if (pl->M < 2) return fail(TEMX_EINVAL, "need at least 2 zonal-mean latitudes");
   HIPCHK(hipSetDevice(pl->device));
-  std::vector<double> p(p_pa_host, p_pa_host + nlev), tab;
+  std::vector<double> p(p_pa_host, p_pa_host + nlev);
   for (int j = 1; j < nlev; ++j)
     if (!(p[j] > p[j - 1])) return fail(TEMX_EINVAL, "pressure must be strictly ascending (front end flips)");
   // a failure below must not leave an earlier configuration half replaced: the plan is unconfigured
@@ -3076,30 +2410,13 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
   const int M = pl->M;
   const int64_t D = pl->D;
   int rc;
-  if ((rc = upload(pl->p, p.data(), (size_t)nlev * 8))) return rc;
-  gradient_table(p, tab);
-  if ((rc = upload(pl->pg, tab.data(), tab.size() * 8))) return rc;
-  // latitude tables: f and cos(lat) use lat*pi/180 (tem_diagnostics.py:401-402), the gradient
-  // uses np.deg2rad(lat) = lat*(pi/180) (:586)
-  std::vector<double> latr(M), cosl(M), fc(M);
-  for (int m = 0; m < M; ++m) {
-    const double lat = pl->lat_out_deg[m];
-    latr[m] = lat * (M_PI / 180.0);
-    cosl[m] = std::cos(lat * M_PI / 180.0);
-    fc[m] = 2 * kOm * std::sin(lat * M_PI / 180.0);
-  }
-  gradient_table(latr, tab);
-  if ((rc = upload(pl->lg, tab.data(), tab.size() * 8))) return rc;
-  if ((rc = upload(pl->coslat, cosl.data(), (size_t)M * 8))) return rc;
-  if ((rc = upload(pl->fcor, fc.data(), (size_t)M * 8))) return rc;
-  // theta = T (p0/p)^k, k = R/Cp  (tem_diagnostics.py:498, constants.py:12): per-column scale
-  std::vector<double> cs((size_t)D);
-  const double kap = kR / kCp;
-  for (int j = 0; j < nlev; ++j) {
-    const double s = std::pow(p0 / p[j], kap);
-    for (int64_t t = 0; t < nt; ++t) cs[(size_t)j * nt + t] = s;
-  }
-  if ((rc = upload(pl->colscale, cs.data(), cs.size() * 8))) return rc;
+  const TemTables tt = tem_tables(p, nt, p0, pl->lat_out_deg);
+  if ((rc = upload(pl->p, p))) return rc;
+  if ((rc = upload(pl->pg, tt.pg))) return rc;
+  if ((rc = upload(pl->lg, tt.lg))) return rc;
+  if ((rc = upload(pl->coslat, tt.coslat))) return rc;
+  if ((rc = upload(pl->fcor, tt.fcor))) return rc;
+  if ((rc = upload(pl->colscale, tt.colscale))) return rc;
 
   const int ndt_ = (int)((D + 15) / 16);
   const int pdpw = proj_dpw(4, ndt_);
@@ -3139,7 +2456,7 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
       if ((rc = pl->partial.ensure(std::max(need4, pl->partial.bytes)))) return rc;
       if ((rc = pl->Bs.ensure((size_t)4 * 64 * D * 8))) return rc;
       const int2* cuts_unused = nullptr;
-      if ((rc = class_cuts(pl, pl->sp_cproj4.nsplit, &cuts_unused, true))) return rc;
+      if ((rc = class_cuts_dev(pl, pl->sp_cproj4.nsplit, &cuts_unused, true))) return rc;
       pl->lone = true;
     }
   }
@@ -3216,8 +2533,8 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
               if ((rc = pl->rho0.ensure((size_t)4 * pl->KR * D * 8))) return rc;
               HIPCHK(hipMemset(pl->rho0.p, 0, pl->rho0.bytes));
               const int2* cu = nullptr;
-              if ((rc = os_cuts(pl, false, pl->sp_os.nsplit, &cu))) return rc;
-              if ((rc = os_cuts(pl, true, pl->sp_os_s.nsplit, &cu))) return rc;
+              if ((rc = os_cuts_dev(pl, false, pl->sp_os.nsplit, &cu))) return rc;
+              if ((rc = os_cuts_dev(pl, true, pl->sp_os_s.nsplit, &cu))) return rc;
               pl->os_on = true;
             }
           }
@@ -3226,10 +2543,10 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
     }
     // work cuts now, not at the first launch: launches must stay legal inside a stream capture
     const int2* cuts_unused = nullptr;
-    if (pl->onepass && (rc = class_cuts(pl, pl->sp_cproj4.nsplit, &cuts_unused, true))) return rc;
-    if (pl->onepass && (rc = class_cuts(pl, pl->sp_copw.nsplit * 4, &cuts_unused, true))) return rc;
+    if (pl->onepass && (rc = class_cuts_dev(pl, pl->sp_cproj4.nsplit, &cuts_unused, true))) return rc;
+    if (pl->onepass && (rc = class_cuts_dev(pl, pl->sp_copw.nsplit * 4, &cuts_unused, true))) return rc;
     for (int nsub : {pl->sp_cproj4.nsplit, pl->sp_cproj1.nsplit, pl->sp_ceddy.nsplit * (8 / edpw)})
-      if ((rc = class_cuts(pl, nsub, &cuts_unused))) return rc;
+      if ((rc = class_cuts_dev(pl, nsub, &cuts_unused))) return rc;
   }
   if (pl->sym) {
     const int64_t nch = (pl->npg + SYM_PROJ_CH - 1) / SYM_PROJ_CH;
@@ -3632,47 +2949,10 @@ static int miss_setup(temx_plan* pl) {
     HIPCHK(hipMemcpy(G2.data(), pl->G.p, G2.size() * 8, hipMemcpyDeviceToHost));
     for (int l = 0; l < K; ++l) T[(size_t)l * K + l] = 1.0;
   }
-  const std::vector<double>& Gi = pl->h_Ginv;   // the default operator: coefficients = Gi Q^T a
-  // s = Y0^T 1 (raw), from the latitudes
   std::vector<double> xs((size_t)pl->N);
   HIPCHK(hipMemcpy(xs.data(), pl->x.p, xs.size() * 8, hipMemcpyDeviceToHost));
-  std::vector<long double> s(K, 0.0L), y(std::max(K, NE));
-  for (int64_t i = 0; i < pl->N; ++i) {
-    ylm0_row(xs[i], K, y.data());
-    for (int l = 0; l < K; ++l) s[l] += y[l];
-  }
-  std::vector<double> tab;
-  tab.reserve((size_t)2 * K * K + (size_t)NQ * (K + NE) + K);
-  tab.insert(tab.end(), G2.begin(), G2.end());
-  std::vector<long double> xq, wq;
-  gauss_legendre(NQ, xq, wq);
-  const long double twopi = 6.283185307179586476925286766559005768L;
-  std::vector<double> Yq((size_t)NQ * NE);
-  for (int q = 0; q < NQ; ++q) {                    // Zq[q][j] = sum_l Y_l(x_q) T[l][j]
-    ylm0_row(xq[q], NE, y.data());
-    for (int j = 0; j < K; ++j) {
-      long double a = 0.0L;
-      for (int l = 0; l <= j; ++l) a += y[l] * T[(size_t)l * K + j];
-      tab.push_back((double)a);
-    }
-    for (int n = 0; n < NE; ++n) Yq[(size_t)q * NE + n] = (double)(twopi * wq[q] * y[n]);
-  }
-  tab.insert(tab.end(), Yq.begin(), Yq.end());
-  std::vector<long double> sQ(K, 0.0L);            // Q^T 1 = T^T s
-  for (int j = 0; j < K; ++j)
-    for (int l = 0; l <= j; ++l) sQ[j] += s[l] * T[(size_t)l * K + j];
-  for (int j = 0; j < K; ++j)                       // Acov = Gi T^T
-    for (int l = 0; l < K; ++l) {
-      long double a = 0.0L;
-      for (int k = 0; k < K; ++k) a += (long double)Gi[(size_t)j * K + k] * T[(size_t)l * K + k];
-      tab.push_back((double)a);
-    }
-  for (int j = 0; j < K; ++j) {                     // c1 = Gi Q^T 1
-    long double a = 0.0L;
-    for (int k = 0; k < K; ++k) a += (long double)Gi[(size_t)j * K + k] * sQ[k];
-    tab.push_back((double)a);
-  }
-  if ((rc = upload(pl->mtab, tab.data(), tab.size() * 8))) return rc;
+  // pl->h_Ginv: the default operator, coefficients = Gi Q^T a
+  if ((rc = upload(pl->mtab, miss_tables(G2.data(), T.data(), pl->h_Ginv.data(), xs.data(), pl->N, K, pl->L)))) return rc;
   HIPCHK(hipDeviceSynchronize());
   pl->miss_built = true;
   return TEMX_OK;

@@ -92,7 +92,7 @@ def _assert_all(what, errs, tol):
 ])
 def test_long_class_sides_vs_oracle(grid, dtype, noise):
     """NLON members per class side.  sweep_os2_kernel adds the members of a side into one fp32 accumulator, so an
-    fp32 plan may not keep a side longer than TEMX_F32_SIDE_CAP = 8 members (temx.hip, build_classes): with the
+    fp32 plan may not keep a side longer than TEMX_F32_SIDE_CAP = 8 members (class_tables.hpp, build_classes): with the
     sides left whole the fp32 cases here miss 2e-5 (a numpy model of the sum gives up to 1e-3 of the covariance at
     3600 members; sides of 32 still gave 1.6e-5 on the reduced grid and 2.5e-5 on the same grid at D = 112).  Single sweep with the row map (the kernels above) and the tile map, and the class-sum form with
     both maps, each against TEMOracle(mode="factorised"): 1e-10 for fp64 fields, 2e-5 for fp32."""

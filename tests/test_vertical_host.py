@@ -128,9 +128,9 @@ VERT_THREADS = 256
 
 
 def slab_shape(nf, nlev, nt, nplev, tsz, psz):
-    """Host mirror of vert_slab_shape (temx.hip), compared with the C++ line by line when it was written: the LDS
-    budget, the 256 / nt cap on cw, seg = max(4, ceil(brackets / most)).  psz is 0 in hybrid mode.  None: the slab map
-    cannot take the shape.  Only the tests use it, to assert that their shapes hit the regimes they name."""
+    """Host mirror of vert_slab_shape (launch_shapes.hpp), which test_slab_shape_mirrors_the_library holds it to: the
+    LDS budget, the 256 / nt cap on cw, seg = max(4, ceil(brackets / most)).  psz is 0 in hybrid mode.  None: the slab
+    map cannot take the shape.  Only the tests use it, to assert that their shapes hit the regimes they name."""
     if nt > VERT_THREADS // 4:
         return None
     in_stride, out_stride = (nlev * nt) | 1, (nplev * nt) | 1
@@ -387,6 +387,27 @@ def test_sweep_shapes_hit_the_regimes_they_name():
     # a block of columns shorter than one 16-byte vector, and nt on both sides of the default map's switch (128-byte rows)
     assert any(c[1] * c[2] * np.dtype(c[4]).itemsize < 16 for c in SWEEP)
     assert {(c[2] * np.dtype(c[4]).itemsize) for c in SWEEP if not c[8] and c[8] is not None} == {120, 128, 124}
+
+
+@pytest.mark.parametrize("build", ["plain", "asan"])
+def test_slab_shape_mirrors_the_library(build, tmp_path_factory):
+    """The real vert_slab_shape, run through tests/host/host_tables_main.cpp on every row of SWEEP and TIE_CASES (and
+    on rows that are too long for the slab map): slab_shape agrees field for field, the refusals included."""
+    from test_host_tables import runner, vert_cases
+    cases = np.concatenate([vert_cases(), [[2, 9, 65, 5, 8, 0], [1, 2, 200, 1, 4, 4]]])
+    out = runner(build, tmp_path_factory)("vert", cases)["vert"].reshape(-1, 10)
+    assert len(cases) == len(SWEEP) + len(TIE_CASES) + 2
+    for (nf, nlev, nt, nplev, tsz, psz), o in zip(cases.astype(np.int64).tolist(), out.tolist()):
+        ok, cw, nseg, seg, in_stride, out_stride, in_img, out_img, p_img, lds = o
+        sh = slab_shape(nf, nlev, nt, nplev, tsz, psz)
+        if sh is None:
+            assert ok == 0, (nf, nlev, nt, nplev, tsz, psz)
+            continue
+        assert ok == 1 and dict(cw=cw, seg=seg, nseg=nseg, in_stride=in_stride, out_stride=out_stride) == sh
+        r16 = lambda b: (b + 15) // 16 * 16
+        assert (in_img, out_img, p_img) == (r16(cw * in_stride * tsz), r16(cw * out_stride * tsz), r16(cw * in_stride * psz))
+        assert lds == VERT_THREADS * 4 + p_img + nf * (in_img + out_img) <= 48 * 1024
+    assert sum(1 for o in out.tolist() if o[0] == 0) == 3
 
 
 def test_unaligned_and_count_fixtures_are_well_conditioned():

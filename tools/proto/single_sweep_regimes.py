@@ -8,7 +8,7 @@ results and the three flux means is the FLOOR of the algebra in exact-order fp64
 and in MFMA blocks; the test holds it to 4 x this floor where the floor is above 2.5e-11, to 1e-10 elsewhere.
 
 The reference is what the engine fits: degree < 16, on the engine's own subsample -- every S-th class-group of the
-row table in table order, S = groups // 32 (temx.hip, build_classes and "subsample of class-groups for the reference
+row table in table order, S = groups // 32 (class_tables.hpp, build_classes and class_subsample: the subsample of class-groups for the reference
 fit"); class_table() restates that order.  `--subsample random` takes a random 1/16 of the columns instead and
 `--subsample all` the whole grid, to see what the choice of the sample costs.  The header line of each grid says how
 the engine's subsample covers the latitudes (the largest gap in |sin lat| between sampled classes).
@@ -40,7 +40,7 @@ FIELD_SEED = 1
 
 
 def class_table(lat, tol=1e-11):
-    """The latitude classes of build_classes (temx.hip) for an fp64 plan, in table order: a list of (rows north,
+    """The latitude classes of build_classes (class_tables.hpp) for an fp64 plan, in table order: a list of (rows north,
     rows south); consecutive runs of 4 are the class-groups."""
     lat = np.asarray(lat, dtype=np.float64)
     order = np.argsort(np.abs(lat), kind="stable")

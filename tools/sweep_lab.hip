@@ -109,7 +109,7 @@ static std::vector<int> group_cuts(const std::vector<int>& gbatch0, int nsub) {
   const int64_t ng = (int64_t)gbatch0.size() - 1, nbatch = gbatch0[ng];
   std::vector<int> cut(2 * (nsub + 1));
   int g = 0;
-  const int64_t gc = getenv("LAB_GROUP_COST") ? atoi(getenv("LAB_GROUP_COST")) : 2;   // batches a group end is worth (temx.hip: class_cuts)
+  const int64_t gc = getenv("LAB_GROUP_COST") ? atoi(getenv("LAB_GROUP_COST")) : 2;   // batches a group end is worth (class_tables.hpp: work_cuts)
   const int64_t total = nbatch + gc * ng;
   for (int k = 0; k <= nsub; ++k) {
     const int64_t want = total * k / nsub;
@@ -356,7 +356,7 @@ int run(int64_t N, int64_t D, int reps, const char* only) {
     static int *d_crowN = nullptr, *d_crowS = nullptr, *d_gfN = nullptr, *d_gfS = nullptr;
     if (!d_crowN) {
       SideTables stb;
-      build_side_tables(crow, gb0, ng, CLS_MB, CLS_PADB, CLS_SOUTH, CLS_FIRST, CLS_LAST, CLS_HASPAD_BIT, stb);
+      build_side_tables(crow, gb0, ng, stb);
       d_crowN = to_dev(stb.crow[0]); d_crowS = to_dev(stb.crow[1]); d_gfN = to_dev(stb.gfirst[0]); d_gfS = to_dev(stb.gfirst[1]);
       printf("side tables: %d northern and %d southern batches\n", stb.gfirst[0].back(), stb.gfirst[1].back());
     }
