@@ -91,6 +91,40 @@ inline LayoutTile layout_tile(int64_t ncol, int nlev, int64_t ntb, size_t dsz) {
   return tl;
 }
 
+// ---- fused ingestion: tile of a launch (kernels_ingest.hpp) -----------------------------------------------------
+// dsz: bytes of a destination element; ssz: bytes of the narrowest source element.
+//   TT   times per tile: 128 bytes of destination (what the lanes of one column write per target level), or the whole
+//        window when it is shorter; halved until two level slots of all nf fields fit INGEST_LDS_BYTES.
+//   TC   columns per tile: 128 bytes of the narrowest source per row on the read side (16 fp64, 32 fp32), more when
+//        TT is short, so that the tile still has a (column, time) pair for every lane.
+//   KW   brackets per level window: as many level slots as the budget holds, less one.
+// false: no tile fits the budget (cannot happen for nf <= 8: TC = 256, TT = 1 takes 2 KiB per field and slot).
+inline bool ingest_tile(int64_t ncol, int nlev, int64_t ntb, int nf, size_t dsz, size_t ssz, IngestTile* tl, size_t* lds) {
+  if (ncol < 1 || nlev < 2 || ntb < 1 || nf < 1) return false;
+  int tt = (int)std::min<int64_t>(ntb, (int64_t)(128 / dsz));
+  for (;; tt = (tt + 1) / 2) {
+    int shift = ssz >= 8 ? 4 : 5;
+    while ((2 << shift) * tt <= INGEST_THREADS) ++shift;
+    const int stride = tt | 1;
+    const size_t img = ((size_t)1 << shift) * stride;
+    const size_t slot = (size_t)nf * img * dsz, psb = img * sizeof(double);
+    const size_t nslot = psb < (size_t)INGEST_LDS_BYTES ? ((size_t)INGEST_LDS_BYTES - psb) / slot : 0;
+    if (nslot >= 2) {
+      tl->tc_shift = shift;
+      tl->tt = tt;
+      tl->kw = (int)std::min<size_t>(nslot - 1, (size_t)nlev - 1);
+      tl->stride = stride;
+      tl->ppl = ((1 << shift) * tt + INGEST_THREADS - 1) / INGEST_THREADS;
+      tl->nct = (int)((ncol + (1 << shift) - 1) >> shift);
+      tl->ntt = (int)((ntb + tt - 1) / tt);
+      tl->nwin = (nlev - 1 + tl->kw - 1) / tl->kw;
+      *lds = psb + (size_t)(tl->kw + 1) * slot;
+      return true;
+    }
+    if (tt == 1) return false;
+  }
+}
+
 }  // namespace temx
 
 #endif

@@ -33,6 +33,22 @@ struct LayoutTile {
   int nct, nlt, ntt;   // tiles along ncol, nlev, ntb
 };
 
+// ---- fused ingestion (kernels_ingest.hpp): tile of a launch, chosen by launch_shapes.hpp, ingest_tile -------------
+constexpr int INGEST_THREADS = 256;
+constexpr int INGEST_LDS_BYTES = 48 * 1024;   // per workgroup: three workgroups per CU, one loads while another walks
+
+// LDS of a workgroup of ingest_kernel: [fp64 ps image] [nf fields][kw + 1 level slots] images of the destination dtype;
+// an image is TC columns of `stride` elements.
+struct IngestTile {
+  int tc_shift;   // TC = 1 << tc_shift columns, 16 .. 256
+  int tt;         // times per tile
+  int kw;         // brackets per level window: a window holds kw + 1 levels, its first the last of the one before
+  int stride;     // LDS elements per column, odd, >= tt
+  int ppl;        // (column, time) pairs per lane: ceil(TC * tt / INGEST_THREADS)
+  int nct, ntt;   // tiles along ncol, ntb
+  int nwin;       // level windows: ceil((nlev - 1) / kw)
+};
+
 }  // namespace temx
 
 #endif

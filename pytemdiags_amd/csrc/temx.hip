@@ -3,6 +3,7 @@
 #include "../../include/temx.h"
 #include "../../include/temx_vert.h"
 #include "../../include/temx_layout.h"
+#include "../../include/temx_ingest.h"
 
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,7 @@
 #include "kernels_miss.hpp"
 #include "kernels_vert.hpp"
 #include "kernels_layout.hpp"
+#include "kernels_ingest.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
 #include "class_tables.hpp"
 #include "host_math.hpp"
@@ -3639,6 +3641,117 @@ int temxl_to_engine(int device, int nf, const void* const* src_host, const int* 
   else
     hipLaunchKernelGGL((layout_to_engine_kernel<uint32_t>), dim3((unsigned)grid), dim3(LAYOUT_THREADS), lds, st, fp, nf,
                        src_f32, ncol, nlev, t0, ntb, flip, tl);
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+} TEMX_CATCH
+
+
+// ---- time-major model-level records to pressure levels in the engine's layout (include/temx_ingest.h) ----
+int temxi_version(void) { return 100; }
+
+int temxi_records_to_pressure(int device, int nf, const void* const* src_host, const int* src_dtype_host,
+                              void* const* dst_host, int dst_dtype, int64_t ncol, int nlev, int64_t nt_src, int64_t t0,
+                              int64_t ntb, int nplev, const double* plev_pa_host, const double* hyam_host,
+                              const double* hybm_host, double p0_hybrid, const void* ps, int ps_dtype, int method,
+                              int edge, void* stream) try {
+  if (nf < 1 || nf > TEMXI_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", (int)TEMXI_NF_MAX, nf);
+  if (!src_host) return fail(TEMX_EINVAL, "src_host is null");
+  if (!src_dtype_host) return fail(TEMX_EINVAL, "src_dtype_host is null");
+  if (!dst_host) return fail(TEMX_EINVAL, "dst_host is null");
+  if (!plev_pa_host || !hyam_host || !hybm_host) return fail(TEMX_EINVAL, "plev_pa_host, hyam_host or hybm_host is null");
+  if (!ps) return fail(TEMX_EINVAL, "ps is null");
+  if (dst_dtype != TEMX_F64 && dst_dtype != TEMX_F32) return fail(TEMX_EINVAL, "dst_dtype must be TEMX_F64 or TEMX_F32");
+  if (ps_dtype != TEMX_F64 && ps_dtype != TEMX_F32) return fail(TEMX_EINVAL, "ps_dtype must be TEMX_F64 or TEMX_F32");
+  if (method != TEMXV_LOG && method != TEMXV_LINEAR) return fail(TEMX_EINVAL, "method must be TEMXV_LOG or TEMXV_LINEAR");
+  if (edge != TEMXV_EDGE_NAN && edge != TEMXV_EDGE_HOLD) return fail(TEMX_EINVAL, "edge must be TEMXV_EDGE_NAN or TEMXV_EDGE_HOLD");
+  if (ncol < 1 || nt_src < 1 || ntb < 1 || nplev < 1 || nlev < 2)
+    return fail(TEMX_EINVAL, "sizes must be positive (nlev at least 2)");
+  if (t0 < 0) return fail(TEMX_EINVAL, "t0 must not be negative");
+  if (nlev > (1 << 20) || nplev > (1 << 20) || nt_src > (int64_t(1) << 31) || ncol > (int64_t(1) << 40))
+    return fail(TEMX_EINVAL, "sizes out of range (ncol, nlev, nplev or nt_src)");
+  if (ntb > nt_src || t0 > nt_src - ntb)
+    return fail(TEMX_EINVAL, "t0 + ntb = %lld exceeds nt_src = %lld", (long long)(t0 + ntb), (long long)nt_src);
+  if ((double)ncol * (double)std::max(nlev, nplev) * (double)nt_src > 281474976710656.0)
+    return fail(TEMX_EINVAL, "sizes out of range (ncol * levels * nt_src above 2^48)");
+  if (!std::isfinite(p0_hybrid)) return fail(TEMX_EINVAL, "p0_hybrid is not finite");
+  for (int j = 0; j < nplev; ++j)
+    if (!(plev_pa_host[j] > 0.0) || !std::isfinite(plev_pa_host[j]) || (j && !(plev_pa_host[j] > plev_pa_host[j - 1])))
+      return fail(TEMX_EINVAL, "plev must be positive, finite and strictly ascending (entry %d)", j);
+  for (int k = 0; k < nlev; ++k)
+    if (!std::isfinite(hyam_host[k]) || !std::isfinite(hybm_host[k]))
+      return fail(TEMX_EINVAL, "hyam / hybm entry %d is not finite", k);
+  const size_t dsz = dst_dtype == TEMX_F64 ? 8 : 4, psz = ps_dtype == TEMX_F64 ? 8 : 4;
+  const size_t src_elems = (size_t)ncol * nlev * nt_src, dst_bytes = (size_t)ncol * nplev * ntb * dsz;
+  const size_t ps_bytes = (size_t)ncol * nt_src * psz;
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+  };
+  if ((uintptr_t)ps % psz) return fail(TEMX_EINVAL, "ps is not aligned to its element size");
+  unsigned src_f32 = 0;
+  size_t ssz = 8;
+  for (int f = 0; f < nf; ++f) {
+    if (src_dtype_host[f] != TEMX_F64 && src_dtype_host[f] != TEMX_F32)
+      return fail(TEMX_EINVAL, "src_dtype %d must be TEMX_F64 or TEMX_F32", f);
+    if (src_dtype_host[f] == TEMX_F64 && dst_dtype == TEMX_F32)
+      return fail(TEMX_EINVAL, "src_dtype %d is TEMX_F64 but dst_dtype is TEMX_F32: this call does not narrow", f);
+    if (src_dtype_host[f] == TEMX_F32) src_f32 |= 1u << f, ssz = 4;
+    if (!src_host[f]) return fail(TEMX_EINVAL, "src %d is null", f);
+    if (!dst_host[f]) return fail(TEMX_EINVAL, "dst %d is null", f);
+    if ((uintptr_t)src_host[f] % (src_dtype_host[f] == TEMX_F64 ? 8 : 4))
+      return fail(TEMX_EINVAL, "src %d is not aligned to its element size", f);
+    if ((uintptr_t)dst_host[f] % dsz) return fail(TEMX_EINVAL, "dst %d is not aligned to its element size", f);
+  }
+  for (int f = 0; f < nf; ++f) {
+    if (overlap(dst_host[f], dst_bytes, ps, ps_bytes)) return fail(TEMX_EINVAL, "dst %d overlaps ps", f);
+    for (int g = 0; g < nf; ++g) {
+      if (overlap(dst_host[f], dst_bytes, src_host[g], src_elems * (src_dtype_host[g] == TEMX_F64 ? 8 : 4)))
+        return fail(TEMX_EINVAL, "dst %d overlaps src %d", f, g);
+      if (g < f && overlap(dst_host[f], dst_bytes, dst_host[g], dst_bytes))
+        return fail(TEMX_EINVAL, "dst %d overlaps dst %d", f, g);
+    }
+  }
+  if (ncol > (int64_t(1) << 34)) return fail(TEMX_EUNSUPPORTED, "too many columns for one launch");
+  IngestTile tl{};
+  size_t lds = 0;
+  if (!ingest_tile(ncol, nlev, ntb, nf, dsz, ssz, &tl, &lds))
+    return fail(TEMX_EUNSUPPORTED, "no tile of this shape fits the LDS budget of %d bytes", (int)INGEST_LDS_BYTES);
+  const int64_t grid = (int64_t)tl.nct * tl.ntt;
+  if (grid >= (int64_t(1) << 32) / INGEST_THREADS)   // HIP takes fewer than 2^32 threads per grid dimension
+    return fail(TEMX_EUNSUPPORTED, "too many tiles for one launch (%lld): move the window in parts", (long long)grid);
+  if (lds > (size_t)INGEST_LDS_BYTES) return fail(TEMX_EINTERNAL, "ingest tile of %zu bytes exceeds its LDS budget", lds);
+
+  // tables: hyam hybm pt xt, the set temxv_interp forms in hybrid mode, through the same cache
+  std::vector<double> host;
+  host.reserve(2 * (size_t)nlev + 2 * (size_t)nplev + 1);
+  host.insert(host.end(), hyam_host, hyam_host + nlev);
+  host.insert(host.end(), hybm_host, hybm_host + nlev);
+  host.insert(host.end(), plev_pa_host, plev_pa_host + nplev);
+  for (int j = 0; j < nplev; ++j) host.push_back(method == TEMXV_LOG ? std::log(plev_pa_host[j]) : plev_pa_host[j]);
+  host.push_back((double)method);
+  HIPCHK(hipSetDevice(device));
+  const double* dev = nullptr;
+  if (int rc = vert_tables(device, host, &dev)) return rc;
+  VertTab tb{};
+  tb.hyam = dev;
+  tb.hybm = dev + nlev;
+  tb.pt = dev + 2 * (size_t)nlev;
+  tb.xt = tb.pt + nplev;
+  IngestPtrs fp{};
+  for (int f = 0; f < nf; ++f) fp.src[f] = src_host[f], fp.dst[f] = dst_host[f];
+  const int ps_f32 = ps_dtype == TEMX_F32, logp = method == TEMXV_LOG, hold = edge == TEMXV_EDGE_HOLD;
+  hipStream_t st = S_(stream);
+#define TEMXI_GO(T, NF)                                                                                              \
+  hipLaunchKernelGGL((ingest_kernel<T, NF>), dim3((unsigned)grid), dim3(INGEST_THREADS), lds, st, fp, nf, src_f32, ncol, \
+                     nlev, t0, ntb, nplev, tb, p0_hybrid, ps, ps_f32, logp, hold, tl)
+  if (dst_dtype == TEMX_F64) {
+    if (nf <= 4) TEMXI_GO(double, 4);
+    else TEMXI_GO(double, INGEST_NFMAX);
+  } else {
+    if (nf <= 4) TEMXI_GO(float, 4);
+    else TEMXI_GO(float, INGEST_NFMAX);
+  }
+#undef TEMXI_GO
   HIPCHK(hipGetLastError());
   return TEMX_OK;
 } TEMX_CATCH

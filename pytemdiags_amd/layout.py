@@ -169,38 +169,45 @@ class HostBlocks:
     host span.  It goes up in consecutive byte chunks through a ring of two pinned buffers of at most
     ``RING_CHUNK_BYTES`` into one of two device upload buffers, on a copy stream; the compute stream waits for the
     block's event and re-lays it out.  Block n + 1 goes up while block n runs.  No host-side transpose and no
-    whole-record tensor on either side."""
+    whole-record tensor on either side.
 
-    def __init__(self, arrays, device, flip_lev, work):
+    The arrays share the time axis and may differ in what follows it (``[nt][nlev_a][ncol]`` with a level count per
+    array, or ``[nt][ncol]``): a slot holds a block of each in its own shape.  ``step(slot_tensors, ntb, out)`` is the
+    work on the compute stream that turns the first ``ntb`` snapshots of a slot into the block's engine-layout
+    tensors (default: the re-layout of all arrays); ``timing`` reports it under ``step_name``."""
+
+    def __init__(self, arrays, device, flip_lev, work, step=None, step_name="relayout_ms"):
         import torch
         self.device, self.flip, self.work = device, bool(flip_lev), work
+        self.step = step if step is not None else (
+            lambda slot, ntb, out: to_engine_layout(slot, 0, ntb, self.flip, self.work, out=out))
+        self.step_name = step_name
         self.host = []
         for a in arrays:
             a = a.numpy() if isinstance(a, torch.Tensor) else a
             self.host.append(a)
         self.tdt = [torch.float32 if a.dtype == np.float32 else torch.float64 for a in self.host]
-        self.timing = {"upload_ms": [], "relayout_ms": [], "tem_ms": []}
+        self.timing = {"upload_ms": [], step_name: [], "tem_ms": []}
         self._marks = []
 
     def start(self, blocks):
         import torch
         self.blocks = list(blocks)
-        nt, nlev, ncol = self.host[0].shape
-        self.nlev, self.ncol = int(nlev), int(ncol)
         self.ntb_max = max(t1 - t0 for t0, t1 in self.blocks)
+        pers = [self.ntb_max * int(np.prod(a.shape[1:])) for a in self.host]       # elements of a block, per array
         with torch.cuda.device(self.device):
             self.copy_stream = torch.cuda.Stream(self.device)
             # two upload slots, each one allocation: a time-major block of every field in its own dtype
-            per = self.ntb_max * self.nlev * self.ncol
-            offs = np.concatenate([[0], np.cumsum([-(-per * a.dtype.itemsize // 512) * 512 for a in self.host])])
+            offs = np.concatenate([[0], np.cumsum([-(-per * a.dtype.itemsize // 512) * 512
+                                                   for per, a in zip(pers, self.host)])])
             self.slots = []
             for _ in range(min(2, len(self.blocks))):
                 raw = torch.empty(int(offs[-1]), dtype=torch.uint8, device=self.device)
-                self.slots.append([raw[int(o):int(o) + per * a.dtype.itemsize].view(dt).view(self.ntb_max, self.nlev, self.ncol)
-                                   for o, a, dt in zip(offs, self.host, self.tdt)])
+                self.slots.append([raw[int(o):int(o) + per * a.dtype.itemsize].view(dt).view((self.ntb_max,) + tuple(a.shape[1:]))
+                                   for o, per, a, dt in zip(offs, pers, self.host, self.tdt)])
         self.uploaded = [None] * len(self.slots)    # event: the slot's block has arrived
         self.consumed = [None] * len(self.slots)    # event: the slot's block has been re-laid out
-        largest = max(self.ntb_max * self.nlev * self.ncol * a.dtype.itemsize for a in self.host)
+        largest = max(per * a.dtype.itemsize for per, a in zip(pers, self.host))
         nring = max(1, min(int(RING_CHUNK_BYTES), largest))
         self.ring = [torch.empty(nring, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         self.ring_np = [r.numpy() for r in self.ring]
@@ -251,7 +258,7 @@ class HostBlocks:
             self._out = None
         a = torch.cuda.Event(enable_timing=True)
         a.record(st)
-        self._out = to_engine_layout(self.slots[slot], 0, ntb, self.flip, self.work, out=self._out)
+        self._out = self.step(self.slots[slot], ntb, self._out)
         b = torch.cuda.Event(enable_timing=True)
         b.record(st)
         self.consumed[slot] = b
@@ -271,7 +278,7 @@ class HostBlocks:
         self._marks[n].append(c)
 
     def close(self):
-        """``timing``: per block, ``upload_ms`` on the copy stream, ``relayout_ms`` and ``tem_ms`` (TEM and tracer runs
+        """``timing``: per block, ``upload_ms`` on the copy stream, ``relayout_ms`` (the step) and ``tem_ms`` (TEM and tracer runs
         up to the gathering of the results) on the compute stream."""
         self.copy_stream.synchronize()
         for m in self._marks:
@@ -279,6 +286,6 @@ class HostBlocks:
                 m[4].synchronize()
             if len(m) == 5:
                 self.timing["upload_ms"].append(m[0].elapsed_time(m[1]))
-                self.timing["relayout_ms"].append(m[2].elapsed_time(m[3]))
+                self.timing[self.step_name].append(m[2].elapsed_time(m[3]))
                 self.timing["tem_ms"].append(m[3].elapsed_time(m[4]))
         self._out = self.slots = self.ring = self.ring_np = None

@@ -14,6 +14,7 @@ Input kinds (the output kind follows the input kind):
 from __future__ import annotations
 
 import os
+import threading
 import warnings
 
 import numpy as np
@@ -27,6 +28,10 @@ DEFAULT_DIMS = {"horz": "ncol", "vert": "plev", "time": "time"}        # tem_dia
 # dtype each stored quantity has in the reference when the inputs are not fp64:
 # theta is promoted to fp64 by the fp64 pressure einsum (tem_diagnostics.py:498); everything
 # downstream of theta, of cos(lat) products or of p_integral is fp64; the rest keeps the input dtype.
+# from_model_levels hands a block source (vertical.DeviceRecordBlocks / HostRecordBlocks) to the constructor it calls,
+# on the calling thread; the constructor's public signature stays as the reference has it
+_pending = threading.local()
+
 _F64_ALWAYS = {"thetab", "vptpb", "dthetab_dp", "ubcoslat", "dubcoslat_dlat", "psi", "psicoslat",
                "dpsicoslat_dlat", "dpsi_dp", "int_vbdp", "thetap", "vptp", "theta"}
 
@@ -38,6 +43,8 @@ class TEMDiagnostics:
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None):
         # ---- blocked run over the time axis (not in the reference): checked before anything touches the device ----
         self.time_block = layout.check_time_block(time_block)
+        self._given_source = getattr(_pending, "source", None)
+        _pending.source = None
         # ---- missing-value mode (not in the reference): checked before anything touches the device ----
         if missing not in ("raise", "mask"):
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (missing,))
@@ -88,7 +95,7 @@ class TEMDiagnostics:
         self._last_tracer = None
         self._after_launch = None
         self.block_timing = None
-        if self.time_block is None:
+        if self.time_block is None and self._block_source is None:
             plan.set_tem(self.NLEV, self.NT, self._p_np, float(self.p0))
             self._res, self._zon, self._cov, self._tres, self._tzon = self._run_block(
                 plan, self._dev_fields, self._dev_q, self.NT)
@@ -140,7 +147,8 @@ class TEMDiagnostics:
         so the record runs in the blocks of ``layout.time_blocks`` and the results are gathered on the zonal grid at
         ``[..., t0:t1]``.  The native-grid fields are not kept."""
         import torch
-        blocks = layout.time_blocks(self.NT, self.time_block)
+        # (a whole run fed by a block source -- time-major model levels -- is one block, and keeps its fields)
+        blocks = layout.time_blocks(self.NT, self.NT if self.time_block is None else self.time_block)
         src = self._block_source
         src.start(blocks)
         big = None
@@ -155,6 +163,8 @@ class TEMDiagnostics:
                 self._after_launch = lambda n=n: src.after_launch(n)
                 out = self._run_block(plan, fs[:4], fs[4:], ntb)
                 src.done(n)
+                if self.time_block is None:
+                    self._dev_fields, self._dev_q = list(fs[:4]), list(fs[4:])
                 del fs
                 if len(blocks) == 1:
                     big = out
@@ -197,7 +207,9 @@ class TEMDiagnostics:
     @property
     def input_path(self):
         """How the inputs reached the engine's layout: ``"relayout"`` (time-major input, the GPU re-layout of
-        ``layout.to_engine_layout``) or ``"torch"`` (any other dims order: permute and contiguous)."""
+        ``layout.to_engine_layout``) or ``"torch"`` (any other dims order: permute and contiguous); from time-major
+        model levels ``"ingest"`` (the fused remap of ``vertical.records_to_pressure_device``) or
+        ``"relayout+interp"`` (the chain of re-layout and interpolation)."""
         return self._input_path
 
     @classmethod
@@ -214,17 +226,27 @@ class TEMDiagnostics:
         the object equals ``TEMDiagnostics(*interp_to_pressure([ua, va, ta, wap], plev, ...), lat_native, plev=...)``.
         Targets below the surface come out NaN: pass ``missing="mask"`` for those (the default raises, as the
         reference does for NaN input).
+
+        Two orders of the axes are served, named by ``dims=`` for raw arrays and by ``.dims`` for labelled ones:
+        ``(horz, vert, time)`` as above, and C-contiguous ``(time, vert, horz)`` with ``ps`` as ``(time, horz)`` --
+        native model output as it lies in a history file.  The time-major record is never transposed on the host or
+        permuted by torch: ``vertical.records_to_pressure_device`` takes it to pressure levels in the engine's layout
+        (``input_path`` is ``"ingest"`` or ``"relayout+interp"``, by ``vertical.FUSED_RECORDS``; ``p_model=`` is served
+        by the chain), and with ``time_block=n`` one block at a time, host arrays and memmaps through the pinned upload
+        ring, so that nothing of whole-record size exists on the device unless the caller put it there.  Any other
+        order raises ``ValueError`` before any device work.
         """
         import torch
         from . import vertical
-        if "dims" in kw:
-            raise ValueError("from_model_levels takes [ncol][lev][time] arrays; dims= is not supported")
         if kw.get("missing", "raise") not in ("raise", "mask"):
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (kw["missing"],))
         if kw.get("missing", "raise") == "mask" and q is not None:
             cls._refuse_masked_tracers()
         qs = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
         given = [ua, va, ta, wap] + qs
+        if cls._model_level_order(given, kw.pop("dims", None), kw.get("dim_names", DEFAULT_DIMS)) == "time-major":
+            return cls._from_time_major_levels(given, lat_native, plev, ps, hyam, hybm, p0_hybrid, p_model, interp,
+                                               edge, kw)
         outs, plev_asc = vertical._interp(given, plev, ps=ps, hyam=hyam, hybm=hybm, p0=p0_hybrid, p=p_model,
                                           method=interp, edge=edge, device=kw.get("device"), on_device=True)
         # (the model-level device copies died with that call: only the pressure-level tensors are held from here on)
@@ -237,6 +259,131 @@ class TEMDiagnostics:
         obj._torch_out = isinstance(v0, torch.Tensor)
         if not raw:
             obj._kind = "xarray" if containers.is_xarray(ua) else "labeled"
+        return obj
+
+    @staticmethod
+    def _model_level_order(given, dims, dim_names):
+        """``"engine"`` for ``(horz, vert, time)`` / ``(horz, vert)`` input, ``"time-major"`` for ``(time, vert, horz)``;
+        ``ValueError`` for mixed kinds and for every other order (host logic only)."""
+        labeled = [containers.is_labeled(x) for x in given]
+        if any(labeled) and not all(labeled):
+            raise ValueError("fields must all be of the same kind")
+        horz, time = dim_names["horz"], dim_names.get("time", DEFAULT_DIMS["time"])
+        orders = set()
+        for x in given:
+            d = tuple(x.dims) if labeled[0] else (None if dims is None else tuple(dims))
+            if d is None or (len(d) in (2, 3) and d[0] == horz and (len(d) == 2 or d[2] == time) and horz not in d[1:]):
+                orders.add("engine")
+            elif len(d) == 3 and d[0] == time and d[2] == horz and d[1] not in (time, horz):
+                orders.add("time-major")
+            else:
+                raise ValueError("from_model_levels takes its fields as (%s, vert, %s) or as C-contiguous (%s, vert, %s) "
+                                 "with ps as (%s, %s); dims %r are neither, and no array is permuted behind the "
+                                 "caller's back" % (horz, time, time, horz, time, horz, d))
+        if len(orders) != 1:
+            raise ValueError("the fields of from_model_levels must all have the same order of dims")
+        return orders.pop()
+
+    @classmethod
+    def _from_time_major_levels(cls, given, lat_native, plev, ps, hyam, hybm, p0_hybrid, p_model, interp, edge, kw):
+        """``from_model_levels`` for C-contiguous ``(time, vert, horz)`` fields: everything that can be refused is
+        refused on the host, then the constructor runs over a block source of ``vertical``."""
+        import torch
+        from . import _vert, vertical
+        accepted = ("the accepted orders are (horz, vert, time) and C-contiguous (time, vert, horz) with ps as "
+                    "(time, horz)")
+        if interp not in _vert.METHODS:
+            raise ValueError("method must be 'log' or 'linear', got %r" % (interp,))
+        if edge not in _vert.EDGES:
+            raise ValueError("edge must be 'nan' or 'hold', got %r" % (edge,))
+        if (ps is None) == (p_model is None):
+            raise ValueError("give exactly one of ps= (hybrid levels, with hyam= and hybm=) and p_model= (pressure of "
+                             "every point)")
+        hybrid = ps is not None
+        if hybrid and (hyam is None or hybm is None):
+            raise ValueError("hybrid levels (ps=) need hyam= and hybm=")
+        plev_asc = vertical._check_plev(plev)
+        time_block = layout.check_time_block(kw.get("time_block"))
+        first = given[0]
+        labeled = containers.is_labeled(first)
+        vals = [x.values if labeled else x for x in given]
+        pin = ps if hybrid else p_model
+        pin = pin.values if containers.is_labeled(pin) else pin
+        fdt = {"float32": torch.float32, "float64": torch.float64}
+
+        def tdtype(v):
+            return fdt.get(str(v.dtype).replace("torch.", ""))
+        for i, v in enumerate(vals + [pin]):
+            what = "field %d" % i if i < len(vals) else ("ps" if hybrid else "p_model")
+            if not isinstance(v, (np.ndarray, torch.Tensor)):
+                raise ValueError("%s must be a numpy array, a torch tensor or a labelled array of one" % what)
+            if tdtype(v) is None:
+                raise ValueError("%s of time-major input must be float64 or float32, got %s" % (what, v.dtype))
+            contiguous = v.flags.c_contiguous if isinstance(v, np.ndarray) else v.is_contiguous()
+            if not contiguous:
+                raise ValueError("%s is not C-contiguous: time-major input is taken as it lies (%s)" % (what, accepted))
+        shape = tuple(vals[0].shape)
+        if len(shape) != 3:
+            raise ValueError("time-major fields must be (time, vert, horz), got %d dims" % len(shape))
+        nt, nlev, ncol = (int(n) for n in shape)
+        for i, v in enumerate(vals):
+            if tuple(v.shape) != shape:
+                raise ValueError("field %d has shape %s, expected %s" % (i, tuple(v.shape), shape))
+        if nlev < 2 or ncol < 1 or nt < 1:
+            raise ValueError("fields need at least one time, two levels and one column, got shape %s" % (shape,))
+        want = (nt, ncol) if hybrid else shape
+        if tuple(pin.shape) != want:
+            raise ValueError("%s has shape %s, expected %s for time-major fields (%s)"
+                             % ("ps" if hybrid else "p_model", tuple(pin.shape), want, accepted))
+        if hybrid:
+            hyam = np.asarray(hyam, dtype=np.float64).ravel()
+            hybm = np.asarray(hybm, dtype=np.float64).ravel()
+            if hyam.shape[0] != nlev or hybm.shape[0] != nlev:
+                raise ValueError("hyam / hybm have %d / %d entries but the fields have %d levels"
+                                 % (hyam.shape[0], hybm.shape[0], nlev))
+            if not (np.all(np.isfinite(hyam)) and np.all(np.isfinite(hybm)) and np.isfinite(p0_hybrid)):
+                raise ValueError("hyam, hybm and p0 must be finite")
+        on_device = [isinstance(v, torch.Tensor) and v.is_cuda for v in vals + [pin]]
+        if hybrid and not any(on_device):     # host record: min / max of the finite ps, read block-wise
+            rng = vertical.finite_range(pin)
+            if rng is not None:
+                vertical.check_hybrid_monotone(hyam, hybm, float(p0_hybrid), *rng)
+
+        # ---- device work from here on ----
+        device = kw.get("device")
+        dev = device if isinstance(device, torch.device) else torch.device("cuda", int(device or 0))
+        tdt = [tdtype(v) for v in vals]
+        work = torch.float32 if set(tdt) == {torch.float32} else torch.float64
+        arrays = vals + [pin]
+        host_fed = not any(on_device)
+        if not host_fed:
+            arrays = [(a if isinstance(a, torch.Tensor) else torch.as_tensor(a)).to(dev) for a in arrays]
+            if hybrid:
+                rng = vertical.finite_range(arrays[-1])
+                if rng is not None:
+                    vertical.check_hybrid_monotone(hyam, hybm, float(p0_hybrid), *rng)
+        # a blocked host-fed run takes the fused call whatever the gate says: the chain's intermediate would be one
+        # more model-level block on the device, which is what the blocks are there to avoid
+        path = "fused" if host_fed and time_block is not None and hybrid else None
+        step = vertical._RecordStep(len(vals), plev_asc * 100.0, hyam, hybm, p0_hybrid, interp, edge, work, not hybrid, path)
+        source = vertical.HostRecordBlocks(arrays, dev, step) if host_fed else vertical.DeviceRecordBlocks(arrays, step)
+        # the constructor sees the shapes and dtypes of the pressure-level fields; the source brings their values
+        stand_in = [torch.empty((ncol, plev_asc.size, nt), dtype=dt, device="meta") for dt in tdt]
+        kw["plev"] = plev_asc
+        if labeled:
+            tname = first.dims[0]
+            try:
+                kw.setdefault("time", np.asarray(containers.coord_of(first, tname)))
+            except Exception:
+                pass
+        _pending.source = source
+        try:
+            obj = cls(*stand_in[:4], lat_native, q=stand_in[4:] if len(stand_in) > 4 else None, **kw)
+        finally:
+            _pending.source = None
+        obj._torch_out = isinstance(vals[0], torch.Tensor)
+        if labeled:
+            obj._kind = "xarray" if containers.is_xarray(first) else "labeled"
         return obj
 
     @staticmethod
@@ -377,7 +524,12 @@ class TEMDiagnostics:
         self._work_dtype = work
         names = ["ua", "va", "ta", "wap"] + ["q{}".format(i) for i in range(self.ntrac)]
         self._block_source = None
-        if self.time_block is not None:
+        if self._given_source is not None:
+            # time-major model levels (from_model_levels): the inputs are shapes only, the source brings the fields
+            self._dev_fields, self._dev_q = None, None
+            self._block_source, self._given_source = self._given_source, None
+            self._input_path = self._block_source.input_path
+        elif self.time_block is not None:
             # blocked run: nothing is made resident here, _run_blocked brings one block at a time
             self._dev_fields, self._dev_q = None, None
             srcs = [raw[k] for k in names]

@@ -13,7 +13,17 @@ import ctypes as C
 
 import numpy as np
 
-from . import _vert, containers
+from . import _ingest, _vert, containers, layout
+
+# Time-major model-level records (``records_to_pressure_device`` with ``path=None``): does the fused kernel
+# (``temxi_records_to_pressure``) serve, per work dtype, or the chain of re-layout and interpolation?  The two give the
+# same bits, so this is a matter of time alone: a dtype is switched on only by a measurement that shows the fused call
+# no slower than the chain in every leg of that dtype of tools/ingest_bench.py, committed as
+# profiles/ingest_bench_mi355x.json (tests/test_ingest_host.py holds the two together).  Measured, four fields: fp64
+# 1.29 (ne120 x 72 -> 37 x 30), 1.06 (ne120 x 72 -> 72 x 16) and 1.14 (ne30 x 72 -> 37 x 92) times faster than the chain;
+# fp32 0.86 at ne120 x 72 -> 37 x 30 -- slower: a level of its 32 x 32 tile takes a third of the LDS budget, so the level
+# windows are one bracket long -- and stays off.
+FUSED_RECORDS = {"float64": True, "float32": False}
 
 
 def _values(x):
@@ -144,10 +154,11 @@ def _interp(fields, plev_hpa, *, ps=None, hyam=None, hybm=None, p0=1e5, p=None, 
     return (res[0] if single else res), plev
 
 
-def interp_device(fields, plev_pa, *, ps=None, p=None, hyam=None, hybm=None, p0=1e5, method="log", edge="nan"):
+def interp_device(fields, plev_pa, *, ps=None, p=None, hyam=None, hybm=None, p0=1e5, method="log", edge="nan", out=None):
     """One ``temxv_interp`` per eight fields.  ``fields``: contiguous device tensors [ncol][nlev][nt] of one dtype;
     ``ps`` [ncol][nt] or ``p`` [ncol][nlev][nt] on the same device; ``plev_pa`` ascending, in Pa.  Returns new tensors
-    [ncol][nplev][nt]; the call is ordered on the current stream."""
+    [ncol][nplev][nt] (or fills ``out``, contiguous tensors of that shape and dtype); the call is ordered on the
+    current stream."""
     import torch
     lib = _vert.load()
     f0 = fields[0]
@@ -161,7 +172,12 @@ def interp_device(fields, plev_pa, *, ps=None, p=None, hyam=None, hybm=None, p0=
     dts = {torch.float64: _vert.F64, torch.float32: _vert.F32}
     dp = C.POINTER(C.c_double)
     with torch.cuda.device(f0.device):
-        outs = [torch.empty((ncol, nplev, nt), dtype=f0.dtype, device=f0.device) for _ in fields]
+        outs = list(out) if out is not None else [
+            torch.empty((ncol, nplev, nt), dtype=f0.dtype, device=f0.device) for _ in fields]
+        for o in outs:
+            if not (o.is_cuda and o.device == f0.device and o.dtype == f0.dtype and o.is_contiguous()
+                    and tuple(o.shape) == (ncol, nplev, nt)) or len(outs) != len(fields):
+                raise ValueError("out needs one contiguous %s tensor of shape %s per field" % (f0.dtype, (ncol, nplev, nt)))
         stream = C.c_void_p(torch.cuda.current_stream(f0.device).cuda_stream)
         for g in range(0, len(fields), _vert.NF_MAX):
             fs, os_ = fields[g:g + _vert.NF_MAX], outs[g:g + _vert.NF_MAX]
@@ -203,3 +219,175 @@ def interp_to_pressure(fields, plev_hpa, *, ps=None, hyam=None, hybm=None, p0=1e
     """
     return _interp(fields, plev_hpa, ps=ps, hyam=hyam, hybm=hybm, p0=p0, p=p, method=method, edge=edge,
                    device=device)[0]
+
+
+# ---- time-major model-level records: window -> pressure levels in engine layout ---------------------------------------
+def records_to_pressure_device(srcs, ps, plev_pa, *, hyam, hybm, p0=1e5, t0=0, ntb=None, method="log", edge="nan",
+                               dtype=None, out=None, path=None):
+    """Device tensors ``[nt][nlev][ncol]`` on hybrid levels and ``ps`` ``[nt][ncol]`` -> list of ``[ncol][nplev][ntb]``
+    tensors: the snapshots ``t0 .. t0 + ntb`` (default: to the end) on the pressure levels ``plev_pa`` (ascending, Pa),
+    in the engine's layout.  The analogue of ``layout.to_engine_layout`` for model-level records.
+
+    ``srcs``: contiguous float64 / float32 tensors of one shape on one device (a single tensor is taken as a list of
+    one), levels top first; ``ps`` float64 or float32.  ``dtype``: float32 when every source is float32, float64
+    otherwise (float32 widens exactly, float64 is never narrowed).  ``out``: tensors to write into instead of new ones.
+
+    ``path="fused"``: one ``temxi_records_to_pressure`` per eight fields -- each model-level element read once.
+    ``path="chain"``: ``to_engine_layout``, a transpose of the ``ps`` window, ``interp_device``.  The two give the same
+    bits; ``path=None`` takes the fused call where ``FUSED_RECORDS`` has the work dtype switched on.  The call is
+    ordered on the current stream."""
+    import torch
+    srcs = [srcs] if isinstance(srcs, torch.Tensor) else list(srcs)
+    if not srcs:
+        raise ValueError("no sources given")
+    if path not in (None, "fused", "chain"):
+        raise ValueError("path must be None, 'fused' or 'chain', got %r" % (path,))
+    if method not in _vert.METHODS:
+        raise ValueError("method must be 'log' or 'linear', got %r" % (method,))
+    if edge not in _vert.EDGES:
+        raise ValueError("edge must be 'nan' or 'hold', got %r" % (edge,))
+    s0 = srcs[0]
+    dts = {torch.float64: _ingest.F64, torch.float32: _ingest.F32}
+    for s in srcs:
+        if not (isinstance(s, torch.Tensor) and s.is_cuda and s.device == s0.device):
+            raise ValueError("records_to_pressure_device needs device tensors on one device")
+        if s.dim() != 3 or tuple(s.shape) != tuple(s0.shape) or not s.is_contiguous():
+            raise ValueError("records_to_pressure_device needs contiguous [nt][nlev][ncol] tensors of one shape")
+        if s.dtype not in dts:
+            raise ValueError("records_to_pressure_device takes float64 and float32, got %s" % s.dtype)
+    nt_src, nlev, ncol = (int(n) for n in s0.shape)
+    if not (isinstance(ps, torch.Tensor) and ps.is_cuda and ps.device == s0.device and ps.is_contiguous()
+            and tuple(ps.shape) == (nt_src, ncol) and ps.dtype in dts):
+        raise ValueError("ps must be a contiguous float64 / float32 tensor of shape %s on %s" % ((nt_src, ncol), s0.device))
+    t0 = int(t0)
+    ntb = nt_src - t0 if ntb is None else int(ntb)
+    if t0 < 0 or ntb < 1 or t0 + ntb > nt_src:
+        raise ValueError("window t0 = %d, ntb = %d does not lie in 0 .. %d" % (t0, ntb, nt_src))
+    if dtype is None:
+        dtype = torch.float32 if all(s.dtype == torch.float32 for s in srcs) else torch.float64
+    if dtype not in dts:
+        raise ValueError("dtype must be float64 or float32, got %s" % (dtype,))
+    plev_pa = np.ascontiguousarray(plev_pa, dtype=np.float64)
+    hyam = np.ascontiguousarray(hyam, dtype=np.float64).ravel()
+    hybm = np.ascontiguousarray(hybm, dtype=np.float64).ravel()
+    if plev_pa.ndim != 1 or plev_pa.size < 1 or hyam.shape[0] != nlev or hybm.shape[0] != nlev:
+        raise ValueError("plev_pa must be 1-d and hyam / hybm must have %d entries" % nlev)
+    nplev = int(plev_pa.shape[0])
+    if path is None:
+        path = "fused" if FUSED_RECORDS[str(dtype).replace("torch.", "")] else "chain"
+    with torch.cuda.device(s0.device):
+        if out is None:            # one allocation for all fields
+            out = torch.empty((len(srcs), ncol, nplev, ntb), dtype=dtype, device=s0.device).unbind(0)
+        out = list(out)
+        if len(out) != len(srcs):
+            raise ValueError("out has %d tensors for %d sources" % (len(out), len(srcs)))
+        for o in out:
+            if not (o.is_cuda and o.device == s0.device and o.dtype == dtype and o.is_contiguous()
+                    and tuple(o.shape) == (ncol, nplev, ntb)):
+                raise ValueError("out needs contiguous %s tensors of shape %s on %s" % (dtype, (ncol, nplev, ntb), s0.device))
+        if path == "chain":
+            eng = layout.to_engine_layout(srcs, t0, ntb, False, dtype)
+            pst = ps[t0:t0 + ntb].t().contiguous()
+            interp_device(eng, plev_pa, ps=pst, hyam=hyam, hybm=hybm, p0=float(p0), method=method, edge=edge, out=out)
+            return out
+        lib = _ingest.load()
+        dp = C.POINTER(C.c_double)
+        stream = C.c_void_p(torch.cuda.current_stream(s0.device).cuda_stream)
+        for g in range(0, len(srcs), _ingest.NF_MAX):
+            ss, oo = srcs[g:g + _ingest.NF_MAX], out[g:g + _ingest.NF_MAX]
+            sp = (C.c_void_p * len(ss))(*[t.data_ptr() for t in ss])
+            sd = (C.c_int * len(ss))(*[dts[t.dtype] for t in ss])
+            op = (C.c_void_p * len(ss))(*[t.data_ptr() for t in oo])
+            _ingest.check(lib.temxi_records_to_pressure(
+                s0.device.index or 0, len(ss), sp, sd, op, dts[dtype], ncol, nlev, nt_src, t0, ntb, nplev,
+                plev_pa.ctypes.data_as(dp), hyam.ctypes.data_as(dp), hybm.ctypes.data_as(dp), float(p0),
+                C.c_void_p(ps.data_ptr()), dts[ps.dtype], _vert.METHODS[method], _vert.EDGES[edge], stream))
+    return out
+
+
+class _RecordStep:
+    """One time block of time-major model-level tensors -> pressure-level engine-layout tensors.  ``tensors`` are the
+    fields, then ``ps`` (hybrid levels) or the pressure field ``p_model`` (then the chain serves: the pressure is
+    re-laid out like one more field and ``temxv_interp`` runs in field mode)."""
+
+    def __init__(self, nf, plev_pa, hyam, hybm, p0, method, edge, work, field_mode, path):
+        self.nf, self.plev_pa, self.hyam, self.hybm, self.p0 = nf, plev_pa, hyam, hybm, float(p0)
+        self.method, self.edge, self.work, self.field_mode = method, edge, work, bool(field_mode)
+        if field_mode:
+            path = "chain"
+        elif path is None:
+            path = "fused" if FUSED_RECORDS[str(work).replace("torch.", "")] else "chain"
+        self.path = path
+        self.input_path = "ingest" if path == "fused" else "relayout+interp"
+
+    def __call__(self, tensors, t0, ntb, out):
+        srcs, pin = list(tensors[:self.nf]), tensors[self.nf]
+        if not self.field_mode:
+            return records_to_pressure_device(srcs, pin, self.plev_pa, hyam=self.hyam, hybm=self.hybm, p0=self.p0, t0=t0,
+                                              ntb=ntb, method=self.method, edge=self.edge, dtype=self.work, out=out,
+                                              path=self.path)
+        eng = layout.to_engine_layout(srcs, t0, ntb, False, self.work)
+        peng = layout.to_engine_layout([pin], t0, ntb, False, pin.dtype)[0]
+        return interp_device(eng, self.plev_pa, p=peng, method=self.method, edge=self.edge, out=out)
+
+
+class DeviceRecordBlocks:
+    """Block source of a TEM run over time-major model-level device tensors: one fused or chained call per block,
+    straight from the caller's tensors.  The device holds the source plus one pressure-level block."""
+
+    def __init__(self, tensors, step):
+        self.tensors, self.step = list(tensors), step
+        self.input_path = step.input_path
+        self._out = None
+        self.timing = None
+
+    def start(self, blocks):
+        self.blocks = list(blocks)
+
+    def get(self, n):
+        t0, t1 = self.blocks[n]
+        if self._out is not None and self._out[0].shape[2] != t1 - t0:
+            self._out = None                      # the short last block: the full one is released first
+        self._out = self.step(self.tensors, t0, t1 - t0, self._out)
+        return self._out
+
+    def after_launch(self, n):
+        pass
+
+    def done(self, n):
+        pass
+
+    def close(self):
+        self._out = None
+
+
+class HostRecordBlocks(layout.HostBlocks):
+    """Block source of a TEM run over time-major model-level host arrays (``np.ndarray``, ``np.memmap``, CPU tensors):
+    the block of every field and of ``ps`` (or of the pressure field) goes up through the two-slot pinned ring of
+    ``layout.HostBlocks``; the step on the compute stream is the fused or chained remap instead of the re-layout, and
+    ``timing`` reports it as ``ingest_ms``."""
+
+    def __init__(self, arrays, device, step):
+        super().__init__(arrays, device, False, step.work, step=lambda slot, ntb, out: step(slot, 0, ntb, out),
+                         step_name="ingest_ms")
+        self.input_path = step.input_path
+
+
+def finite_range(ps, rows=4096):
+    """(min, max) of the finite values of ``ps`` [nt][...], or None when there are none; a host array is read
+    ``rows`` snapshots at a time (a memmap is never loaded whole), a device tensor in one reduction."""
+    import torch
+    lo, hi = np.inf, -np.inf
+    if isinstance(ps, torch.Tensor) and ps.is_cuda:
+        fin = torch.isfinite(ps)
+        if bool(fin.any()):
+            lo = float(torch.where(fin, ps, torch.full_like(ps, float("inf"))).min())
+            hi = float(torch.where(fin, ps, torch.full_like(ps, float("-inf"))).max())
+    else:
+        a = ps.numpy() if isinstance(ps, torch.Tensor) else ps
+        for r in range(0, a.shape[0], rows):
+            blk = np.asarray(a[r:r + rows])
+            blk = blk[np.isfinite(blk)]
+            if blk.size:
+                lo, hi = min(lo, float(blk.min())), max(hi, float(blk.max()))
+    return None if lo > hi else (lo, hi)
