@@ -88,6 +88,14 @@ enum {
                                       (0..1000, default 500; 0 disables the coverage mask) */
   TEMX_OPT_MISSING_WEIGHT = 10,    /* missing-value mode: tau = 10^-value, the weight of a missing point as an
                                       observation of 0 (4..14, default 10) */
+  TEMX_OPT_LAT_BINS = 12,          /* latitude bins (see "Latitude-bin form" below): 0 = off (default), -1 = the library's
+                                      default B = 512, otherwise B in {128, 256, 512, 1024, 2048}.  Takes effect for the TEM
+                                      pipeline at the next temx_plan_set_tem, for temx_project / temx_zonal_mean at once;
+                                      0 restores the plan's own path completely.  TEMX_EUNSUPPORTED for L > 63, weights-mode
+                                      plans, plans finalised through the pseudo-inverse and plans in missing-value mode;
+                                      TEMX_EINVAL for any other B, and when no J serves (L, B) */
+  TEMX_OPT_BIN_DEGREE = 13,        /* read only: temx_plan_option returns the number J of Chebyshev terms per bin the
+                                      library chose for (L, B), 0 while bins are off */
   TEMX_OPT_OS_SYNC = 11            /* single sweep of fp64 fields, how the four waves of a workgroup hand the class sums
                                       of a class-group over: 0 through counters in LDS, no wave waits for the slowest
                                       (default), 1 through two workgroup barriers (A/B; env: TEMX_OS_SYNC=barrier).
@@ -114,13 +122,32 @@ enum {
  *   Entry points: temx_zonal_mean (native 0 and 1), temx_tem_run, temx_tem_eddy and temx_tem_eddy_rows run masked;
  *     temx_status reports 0 (non-finite input is data).  The staged, sharded and single-sweep entry points and every
  *     tracer entry point return TEMX_EUNSUPPORTED in this mode. */
+ /* Latitude-bin form (TEMX_OPT_LAT_BINS = B; opt-in, nothing selects it).
+ *   For grids whose columns share no latitude (MPAS, ICON, a remapped file with noisy latitudes, any unstructured set),
+ *     where the plan runs the generic sweeps: one row of K = L + 1 harmonics of matrix work per column.
+ *   phi in [-pi/2, pi/2] is cut into B uniform bins of half-width h = pi / (2 B); a column on an inner edge belongs to
+ *     the upper bin.  Inside a bin Y_l^0(phi) is replaced by its Chebyshev interpolant in s = (phi - centre) / h with J
+ *     terms, J the smallest of {8, 10, 12} with 2 (L h / 2)^J / J! <= 1e-13 (TEMX_OPT_BIN_DEGREE reports it): the same
+ *     operator to that accuracy.  A column then costs J multiply-adds per field and read instead of K; the work of size
+ *     K is done once per bin.  The eddies are the exact x - xbar of the two-pass form; the fields are read twice.
+ *   Runs on any grid (class grids included) and ignores TEMX_OPT_FORM and the path overrides; temx_plan_option(
+ *     TEMX_OPT_FORM) reports TEMX_FORM_BINNED, temx_plan_sweep_mode keeps reporting what the latitudes gave.
+ *   Entry points: temx_tem_run (results and zonal intermediates), temx_project, temx_zonal_mean (native 0 and 1) run
+ *     binned.  temx_tem_run leaves B4, C4, the zonal means and the stage state as the two-pass form does: temx_tem_eddy,
+ *     temx_tem_eddy_rows, temx_tracer_run and temx_tracers_run then run the plan's own (two-pass) kernels.  The staged
+ *     (temx_tem_stage*, temx_tracer_stage*, temx_tem_tracer_stage1), sharded (*_from_sums, temx_tem_tail_from_sums) and
+ *     single-sweep (temx_tem_os_*, temx_tracers_os_*) entry points return TEMX_EUNSUPPORTED in this mode.
+ *   Tables and workspace (sorted rows, coefficient tables, chunk moments, per-bin series) are built at the first binned
+ *     temx_plan_set_tem / operator call and freed with the plan; TEMX_ENOMEM with the byte count when they do not fit.
+ *   Configuring TEMX_OPT_MISSING = 1 while bins are in effect fails with TEMX_EUNSUPPORTED, as bins on a masked plan do. */
 enum {
   TEMX_FORM_AUTO = -1,
   TEMX_FORM_TWO_PASS = 0,          /* fields read twice (project sweep, eddy sweep) */
   TEMX_FORM_CLASS_SUMS = 1,        /* one pass with per-class sums + flux kernel wherever possible, never the single sweep */
   TEMX_FORM_SINGLE_SWEEP = 2,      /* the single sweep wherever its instantiations exist */
   TEMX_FORM_NO_SINGLE_SWEEP = 3,   /* automatic choice between the two forms above by problem size, never the single sweep */
-  TEMX_FORM_MASKED = 4             /* reported while missing-value mode is in effect: masked two-pass sweeps (any grid) */
+  TEMX_FORM_MASKED = 4,            /* reported while missing-value mode is in effect: masked two-pass sweeps (any grid) */
+  TEMX_FORM_BINNED = 5             /* reported while latitude bins are in effect (TEMX_OPT_LAT_BINS): binned two-pass sweeps (any grid) */
 };
 
 /* which matrix temx_get_matrix copies */

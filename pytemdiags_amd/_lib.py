@@ -25,9 +25,16 @@ OPT_FORM, OPT_OS_MAP, OPT_OP_MAP, OPT_OS_SUBSAMPLE, OPT_TRACER_ONE_PASS, OPT_SIN
 # missing-value mode (include/temx.h): 0 raise / 1 mask, coverage threshold in per mille, tau = 10^-value
 OPT_MISSING, OPT_MIN_COVERAGE, OPT_MISSING_WEIGHT = 8, 9, 10
 OPT_OS_SYNC = 11          # single sweep of fp64 fields: 0 hand-over by LDS flags (default), 1 by workgroup barriers (A/B)
+# latitude-bin form (include/temx.h): bins (0 off, -1 the library's default), and the Chebyshev terms per bin it chose
+OPT_LAT_BINS, OPT_BIN_DEGREE = 12, 13
+LAT_BINS_ALLOWED = (128, 256, 512, 1024, 2048)
+LAT_BINS_DEFAULT = 512    # what -1 selects (BIN_DEFAULT of csrc/bin_tables.hpp)
 MISSING_MODES = {"raise": 0, "mask": 1}
 FORM_AUTO, FORM_TWO_PASS, FORM_CLASS_SUMS, FORM_SINGLE_SWEEP, FORM_NO_SINGLE_SWEEP = -1, 0, 1, 2, 3
 FORM_MASKED = 4
+FORM_BINNED = 5
+FORM_NAMES = {FORM_TWO_PASS: "two-pass", FORM_CLASS_SUMS: "class-sums", FORM_SINGLE_SWEEP: "single-sweep",
+              FORM_MASKED: "masked", FORM_BINNED: "binned"}
 FORMS = {"auto": FORM_AUTO, "two-pass": FORM_TWO_PASS, "class-sums": FORM_CLASS_SUMS,
          "single-sweep": FORM_SINGLE_SWEEP, "no-single-sweep": FORM_NO_SINGLE_SWEEP}
 

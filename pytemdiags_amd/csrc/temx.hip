@@ -29,10 +29,12 @@
 #include "kernels_op2.hpp"
 #include "kernels_osc.hpp"
 #include "kernels_miss.hpp"
+#include "kernels_bin.hpp"
 #include "kernels_vert.hpp"
 #include "kernels_layout.hpp"
 #include "kernels_ingest.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
+#include "bin_tables.hpp"
 #include "class_tables.hpp"
 #include "host_math.hpp"
 #include "launch_shapes.hpp"
@@ -209,6 +211,17 @@ struct temx_plan {
   DevBuf mtab;                         // G2 [K][K], Zq [NQ][K], Yq [NQ][NE], Acov [K][K], c1 [K]
   DevBuf mB, mC, mCcov, mcov, mZ;      // sums [4K + NE][D], coefficients [4][K4][D], coverage coefficients [K4][D],
                                        // coverage [M][D], zonal scratch of the native operator [M][D]
+  // latitude-bin form (kernels_bin.hpp, bin_tables.hpp; TEMX_OPT_LAT_BINS): nothing here is built or allocated before the
+  // first binned temx_plan_set_tem / operator call
+  int opt_lat_bins = 0;                // B in effect, 0 = off
+  int bin_J = 0, bin_KP = 0;           // Chebyshev terms per bin (8, 10 or 12), K rounded up to a multiple of 16
+  int bin_built = 0;                   // the B the tables on the device were built for (0: none, or another basis since)
+  int bin_pass = 0;                    // > 0 inside a run entry point that goes through the staged ones (temx_tracer_run)
+  int64_t bin_nchunk = 0;
+  std::vector<double> h_lat;           // native latitudes in degrees, as given (the bins are cut in phi, not in cos(colat))
+  DevBuf bin_a, bin_chunk, bin_c0, bin_rows, bin_s;   // a[B][J][KP], chunk list [nchunk] int4, first chunk per bin [B + 1], sorted rows, their s
+  DevBuf bin_T;                        // [2][KP][KP]: T^T (sums Y -> Q) and T (coefficients Q -> Y), zero padded; identities without Q
+  DevBuf bin_cm, bin_z, bin_cy;        // chunk moments [nchunk][NF][J][Dpad], series [B][NF][J][Dpad], Y coefficients [NF][K][D]
   // timing hooks
   bool timing = false;
   std::vector<TimedLaunch> timed[2];
@@ -1259,6 +1272,8 @@ static inline bool tail_is_whole(const temx_plan* pl) { return pl->tt0 == 0 && p
 
 static int tem_stage3_impl(temx_plan* pl, const double* B3, double* results, double* zonal, hipStream_t st);
 static int tem_epilogue(temx_plan* pl, double* results, double* zonal, hipStream_t st);
+static int bin_project_op(temx_plan* pl, const void* A, int dtype, int64_t D, double* B, hipStream_t st);
+static int bin_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* out, int native, hipStream_t st);
 static int miss_check(const temx_plan* pl);
 static int miss_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* out, int native, hipStream_t st);
 static int tracer_stage3_impl(temx_plan* pl, const double* Bq2, double* tres, double* tzon, hipStream_t st);
@@ -1524,6 +1539,63 @@ static int tracer_run_os(temx_plan* pl, int nq, const void* const* q, const void
 
 // ---- missing-value mode: launchers (kernels_miss.hpp) ---------------------------------------------------------
 static inline bool miss_mode(const temx_plan* pl) { return pl->opt_missing == 1; }
+// latitude-bin form (TEMX_OPT_LAT_BINS): the staged, sharded and single-sweep entry points are refused unless a run
+// entry point of this library is what calls them (temx_tracer_run goes through the tracer stages)
+static inline bool bin_mode(const temx_plan* pl) { return pl->opt_lat_bins > 0; }
+static inline bool bin_refused(const temx_plan* pl) { return bin_mode(pl) && pl->bin_pass == 0; }
+struct BinPass {
+  temx_plan* pl;
+  explicit BinPass(temx_plan* p) : pl(p) { ++pl->bin_pass; }
+  ~BinPass() { --pl->bin_pass; }
+};
+static int bin_refuse(const char* what) {
+  return fail(TEMX_EUNSUPPORTED, "%s is not available while latitude bins are in effect (TEMX_OPT_LAT_BINS): the binned form "
+              "serves temx_tem_run, temx_project and temx_zonal_mean", what);
+}
+
+#define TEMX_BIN_J(CALL)                                   \
+  switch (pl->bin_J) {                                     \
+    case 8: CALL(8); break;                                \
+    case 10: CALL(10); break;                              \
+    default: CALL(12); break;                              \
+  }
+#define TEMX_BIN_KP(CALL)                                  \
+  switch (pl->bin_KP) {                                    \
+    case 16: CALL(16); break;                              \
+    case 32: CALL(32); break;                              \
+    case 48: CALL(48); break;                              \
+    default: CALL(64); break;                              \
+  }
+
+static inline dim3 bin_sweep_grid(const temx_plan* pl, int64_t D) {
+  const int Dw = (int)((D + 63) / 64);
+  return dim3((unsigned)(pl->bin_nchunk * ((Dw + 3) / 4)));
+}
+
+// pass 1: chunk moments of NF fields
+template <int NF>
+static int launch_bin_moments(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int64_t D, const double* colscale, int sfield,
+                              hipStream_t st) {
+  const int Dw = (int)((D + 63) / 64);
+  if ((int64_t)pl->bin_nchunk * ((Dw + 3) / 4) >= ((int64_t)1 << 31)) return fail(TEMX_EUNSUPPORTED, "latitude bins: too many work units");
+  const dim3 grid = bin_sweep_grid(pl, D);
+  const int4* ch = static_cast<const int4*>(pl->bin_chunk.p);
+  const int* rows = static_cast<const int*>(pl->bin_rows.p);
+#define TEMX_LBM(Jv)                                                                                                   \
+  do {                                                                                                                 \
+    if (dtype == TEMX_F64)                                                                                             \
+      hipLaunchKernelGGL((bin_moments_kernel<double, NF, Jv>), grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), \
+                         colscale, sfield, pl->bin_cm.d());                                                            \
+    else                                                                                                               \
+      hipLaunchKernelGGL((bin_moments_kernel<float, NF, Jv>), grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), \
+                         colscale, sfield, pl->bin_cm.d());                                                            \
+  } while (0)
+  TEMX_BIN_J(TEMX_LBM)
+#undef TEMX_LBM
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
 static inline double miss_thr(const temx_plan* pl) { return pl->opt_min_cov / 1000.0; }
 static inline double miss_omt(const temx_plan* pl) { return 1.0 - std::pow(10.0, -(double)pl->opt_miss_w); }
 static int miss_refuse(const char* what) {
@@ -1725,6 +1797,7 @@ void temx_plan_destroy(temx_plan* pl) {
                     &pl->rho0, &pl->gaunt, &pl->wq2, &pl->Axq, &pl->rho_t, &pl->Gx, &pl->Gsinv, &pl->Ax, &pl->Axs, &pl->oscblk, &pl->osAt, &pl->osAb, &pl->osAtq, &pl->osAbq, &pl->Bqp})
     b->release();
   for (DevBuf* b : {&pl->eblk, &pl->mtab, &pl->mB, &pl->mC, &pl->mCcov, &pl->mcov, &pl->mZ}) b->release();
+  for (DevBuf* b : {&pl->bin_a, &pl->bin_chunk, &pl->bin_c0, &pl->bin_rows, &pl->bin_s, &pl->bin_T, &pl->bin_cm, &pl->bin_z, &pl->bin_cy}) b->release();
   for (auto& kv : pl->csplits_s) kv.second.release();
   for (auto& kv : pl->csplits) kv.second.release();
   for (int w = 0; w < 2; ++w)
@@ -1839,6 +1912,7 @@ int temx_plan_create(temx_plan** out, int device, int64_t ncol, int L, int M,
   pl->K4 = 4 * pl->stride;
   pl->M = M;
   pl->lat_out_deg.assign(lat_out_deg_host, lat_out_deg_host + M);
+  pl->h_lat.assign(lat_deg_host, lat_deg_host + ncol);
   int rc = TEMX_OK;
   auto bail = [&](int code) {
     temx_plan_destroy(pl);
@@ -2081,6 +2155,7 @@ int temx_plan_finalize(temx_plan* pl, const double* G_host) try {
   pl->finalized = true;
   pl->op_valid = pl->c4_valid = pl->xb_valid = pl->tq_valid = false;   // sums / coefficients of another basis
   pl->miss_built = pl->miss_valid = false;
+  pl->bin_built = 0;
   // one process owns all the rows: second pass of the re-orthogonalisation with its own Gram matrix of Q
   if (want_q && !G_host) return temx_plan_refine(pl, nullptr);
   return TEMX_OK;
@@ -2109,6 +2184,7 @@ int temx_plan_refine(temx_plan* pl, const double* G2_host) try {
   if (spd_factor(G2.data(), K, Li) != 0) return TEMX_OK;   // (cannot happen for Q^T Q ~ I; keep the identity)
   inverse_from_factor(Li, K, Gi.data());
   pl->miss_built = pl->miss_valid = false;
+  pl->bin_built = 0;
   return set_ginv(pl, Gi.data());
 } TEMX_CATCH
 
@@ -2149,6 +2225,7 @@ int temx_plan_set_weights(temx_plan* pl, const double* w_host) try {
   pl->weighted = true;
   pl->finalized = true;
   pl->miss_built = pl->miss_valid = false;
+  pl->bin_built = 0;
   return TEMX_OK;
 } TEMX_CATCH
 
@@ -2245,6 +2322,7 @@ int temx_project(temx_plan* pl, const void* A, int dtype, int64_t D, double* B, 
   if (!pl || !A || !B) return fail(TEMX_EINVAL, "null argument");
   if (D < 1 || D >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "D must be in [1, 2^28)");
   HIPCHK(hipSetDevice(pl->device));
+  if (bin_mode(pl)) return bin_project_op(pl, A, dtype, D, B, S_(stream));
   FieldPtrs<1> fp;
   fp.p[0] = A;
   if (pl->cls) {      // class sweep: one basis row per latitude class
@@ -2263,6 +2341,7 @@ int temx_project(temx_plan* pl, const void* A, int dtype, int64_t D, double* B, 
 int temx_zonal_mean_from_sums(temx_plan* pl, const double* B, int64_t D, double* out, int native,
                               void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_zonal_mean_from_sums");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_zonal_mean_from_sums");
   if (!pl || !B || !out) return fail(TEMX_EINVAL, "null argument");
   if (!pl->finalized) return fail(TEMX_ESTATE, "plan not finalised");
   HIPCHK(hipSetDevice(pl->device));
@@ -2278,6 +2357,7 @@ int temx_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* 
   if (!pl || !A || !out) return fail(TEMX_EINVAL, "null argument");
   if (!pl->finalized) return fail(TEMX_ESTATE, "plan not finalised");
   if (miss_mode(pl)) return miss_zonal_mean(pl, A, dtype, D, out, native, S_(stream));
+  if (bin_mode(pl)) return bin_zonal_mean(pl, A, dtype, D, out, native, S_(stream));
   int rc = pl->opB.ensure((size_t)pl->K * std::max<int64_t>(D, 1) * 8);
   if (rc) return rc;
   if ((rc = temx_project(pl, A, dtype, D, pl->opB.d(), stream))) return rc;
@@ -2292,6 +2372,8 @@ struct FormChoice {
 };
 static FormChoice form_choice(const temx_plan* pl) {
   FormChoice c{false, false, -1};
+  if (bin_mode(pl)) return FormChoice{true, false, 0};   // the binned form ignores the overrides; what runs next to it
+                                                         // (eddies, tracers) is the plan's two-pass form
   switch (pl->opt_form) {
     case TEMX_FORM_TWO_PASS: c.two_pass = true; c.os = 0; break;
     case TEMX_FORM_CLASS_SUMS: c.force_op = true; c.os = 0; break;
@@ -2318,6 +2400,9 @@ static bool tracer_one_pass_wanted(const temx_plan* pl) {
   return pl->opt_tracer_one_pass == 1;
 }
 
+static int bin_check(const temx_plan* pl);
+static int bin_set_tem(temx_plan* pl);
+
 int temx_plan_configure(temx_plan* pl, int option, int value) try {
   if (!pl) return fail(TEMX_EINVAL, "null plan");
   switch (option) {
@@ -2337,8 +2422,10 @@ int temx_plan_configure(temx_plan* pl, int option, int value) try {
     case TEMX_OPT_OS_CONTRACT: pl->opt_os_contract = value; break;
     case TEMX_OPT_MISSING:
       if (value != 0 && value != 1) return fail(TEMX_EINVAL, "TEMX_OPT_MISSING: 0 (raise) or 1 (mask), got %d", value);
-      if (value == 1)
+      if (value == 1) {
+        if (bin_mode(pl)) return fail(TEMX_EUNSUPPORTED, "missing-value mode is not available while latitude bins are in effect (TEMX_OPT_LAT_BINS)");
         if (int rc = miss_check(pl)) return rc;
+      }
       pl->opt_missing = value;
       pl->miss_valid = false;
       break;
@@ -2354,6 +2441,20 @@ int temx_plan_configure(temx_plan* pl, int option, int value) try {
       if (value != 0 && value != 1) return fail(TEMX_EINVAL, "TEMX_OPT_OS_SYNC: 0 (flags) or 1 (barriers), got %d", value);
       pl->opt_os_sync = value;
       break;
+    case TEMX_OPT_LAT_BINS: {
+      const int B = value == -1 ? BIN_DEFAULT : value;
+      if (B != 0) {
+        if (!bin_count_ok(B)) return fail(TEMX_EINVAL, "TEMX_OPT_LAT_BINS: 0 (off), -1 (default, %d) or one of 128, 256, 512, 1024, 2048, got %d", BIN_DEFAULT, value);
+        if (int rc = bin_check(pl)) return rc;
+        if (bin_degree(pl->L, B) == 0)
+          return fail(TEMX_EINVAL, "TEMX_OPT_LAT_BINS: (L, B) = (%d, %d): no Chebyshev degree up to %d keeps the basis rows to %.0e; use more bins",
+                      pl->L, B, BIN_MAX_DEGREE, BIN_BOUND);
+      }
+      pl->opt_lat_bins = B;
+      pl->bin_J = B ? bin_degree(pl->L, B) : 0;
+      break;
+    }
+    case TEMX_OPT_BIN_DEGREE: return fail(TEMX_EINVAL, "TEMX_OPT_BIN_DEGREE is chosen by the library (read it with temx_plan_option)");
     default: return fail(TEMX_EINVAL, "unknown option %d", option);
   }
   pl->tem = false;                // the choice is made in temx_plan_set_tem: call it (again)
@@ -2365,6 +2466,7 @@ int temx_plan_option(const temx_plan* pl, int option) try {
   switch (option) {
     case TEMX_OPT_FORM:
       if (miss_mode(pl)) return TEMX_FORM_MASKED;
+      if (bin_mode(pl)) return TEMX_FORM_BINNED;
       return pl->os_on ? TEMX_FORM_SINGLE_SWEEP : ((pl->cls && pl->onepass) || (pl->lcls && pl->lone) ? TEMX_FORM_CLASS_SUMS : TEMX_FORM_TWO_PASS);
     case TEMX_OPT_OS_MAP: return tile_map(pl->opt_os_map, "TEMX_OS_MAP") ? 1 : 0;
     case TEMX_OPT_OP_MAP: return tile_map(pl->opt_op_map, "TEMX_OP_MAP") ? 1 : 0;
@@ -2376,6 +2478,8 @@ int temx_plan_option(const temx_plan* pl, int option) try {
     case TEMX_OPT_MIN_COVERAGE: return pl->opt_min_cov;
     case TEMX_OPT_MISSING_WEIGHT: return pl->opt_miss_w;
     case TEMX_OPT_OS_SYNC: return os_barrier_wanted(pl) ? 1 : 0;
+    case TEMX_OPT_LAT_BINS: return pl->opt_lat_bins;
+    case TEMX_OPT_BIN_DEGREE: return pl->bin_J;
     default: return -1;
   }
 } TEMX_CATCH
@@ -2565,6 +2669,7 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
                                            pl->sp_sproj1.nsplit}) * pl->K * D * 8;
     if ((rc = pl->partial.ensure(std::max(need2, pl->partial.bytes)))) return rc;
   }
+  if (bin_mode(pl) && (rc = bin_set_tem(pl))) return rc;   // tables (first time) and the workspace of the binned sweeps
   pl->tem = true;
   return TEMX_OK;
 } TEMX_CATCH
@@ -2579,6 +2684,7 @@ static int tem_ready(temx_plan* pl) {
 int temx_tem_stage1(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                     int dtype, double* B4, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_stage1");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_stage1");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !B4) return fail(TEMX_EINVAL, "null argument");
@@ -2696,6 +2802,7 @@ static int tem_stage2_large(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, co
 int temx_tem_stage2(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                     int dtype, const double* B4, double* B3, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_stage2");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_stage2");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !B4 || !B3) return fail(TEMX_EINVAL, "null argument");
@@ -2716,6 +2823,7 @@ int temx_tem_stage2(temx_plan* pl, const void* ua, const void* va, const void* t
 
 int temx_tem_stage2_from_sums(temx_plan* pl, const double* B4, double* B3, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_stage2_from_sums");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_stage2_from_sums");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!B4 || !B3) return fail(TEMX_EINVAL, "null argument");
@@ -2745,6 +2853,7 @@ int temx_tem_stage2_from_sums(temx_plan* pl, const double* B4, double* B3, void*
 
 int temx_tem_stage3(temx_plan* pl, const double* B3, double* results, double* zonal, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_stage3");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_stage3");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!B3 || !results) return fail(TEMX_EINVAL, "null argument");
@@ -2810,6 +2919,7 @@ static int slices_ok(const temx_plan* pl, int nslices) {
 int temx_tem_os_prepass(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap, int dtype,
                         double* As, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_os_prepass");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_os_prepass");
   int rc = os_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !As) return fail(TEMX_EINVAL, "null argument");
@@ -2821,6 +2931,7 @@ int temx_tem_os_prepass(temx_plan* pl, const void* ua, const void* va, const voi
 int temx_tem_os_sweep(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap, int dtype,
                       const double* As, int nslices, double* proj, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_os_sweep");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_os_sweep");
   int rc = os_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !As || !proj) return fail(TEMX_EINVAL, "null argument");
@@ -2833,6 +2944,7 @@ int temx_tem_os_sweep(temx_plan* pl, const void* ua, const void* va, const void*
 int temx_tem_os_tail(temx_plan* pl, const double* proj_slice, int64_t t0, int64_t nts, double* results, double* zonal,
                      void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_os_tail");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_os_tail");
   int rc = os_ready(pl);
   if (rc) return rc;
   if (!proj_slice || !results) return fail(TEMX_EINVAL, "null argument");
@@ -2854,6 +2966,7 @@ static int tracers_args(const temx_plan* pl, int nq, const void* const* q_host, 
 int temx_tracers_os_prepass(temx_plan* pl, int nq, const void* const* q_host, const void* va, const void* wap, int dtype,
                             double* Asq, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tracers_os_prepass");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tracers_os_prepass");
   int rc = os_ready(pl);
   if (rc) return rc;
   if ((rc = tracers_args(pl, nq, q_host, va, wap, dtype))) return rc;
@@ -2865,6 +2978,7 @@ int temx_tracers_os_prepass(temx_plan* pl, int nq, const void* const* q_host, co
 int temx_tracers_os_sweep(temx_plan* pl, int nq, const void* const* q_host, const void* va, const void* wap, int dtype,
                           const double* Asq, int nslices, double* projq, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tracers_os_sweep");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tracers_os_sweep");
   int rc = os_ready(pl);
   if (rc) return rc;
   if ((rc = tracers_args(pl, nq, q_host, va, wap, dtype))) return rc;
@@ -2877,6 +2991,7 @@ int temx_tracers_os_sweep(temx_plan* pl, int nq, const void* const* q_host, cons
 int temx_tracers_os_tail(temx_plan* pl, int nq, const double* projq_slice, double* const* tres_host, double* const* tzon_host,
                          void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tracers_os_tail");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tracers_os_tail");
   int rc = os_ready(pl);
   if (rc) return rc;
   if (nq != 1 && nq != 2) return fail(TEMX_EINVAL, "nq = %d: one or two tracers per sweep", nq);
@@ -2892,6 +3007,7 @@ int temx_tracers_os_tail(temx_plan* pl, int nq, const double* projq_slice, doubl
 int temx_tem_tail_from_sums(temx_plan* pl, const double* B4s, const double* B3s, int64_t t0, int64_t nts, double* results,
                             double* zonal, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_tail_from_sums");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_tail_from_sums");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!B4s || !B3s || !results) return fail(TEMX_EINVAL, "null argument");
@@ -3026,6 +3142,198 @@ static int miss_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, d
   return TEMX_OK;
 }
 
+// ---- latitude-bin form (kernels_bin.hpp, bin_tables.hpp): tables, the binned TEM run and the binned operator ---------
+// configurations the binned form serves (checked at temx_plan_configure and again before every binned run)
+static int bin_check(const temx_plan* pl) {
+  if (pl->K > 64) return fail(TEMX_EUNSUPPORTED, "latitude bins: L = %d, this version supports L <= 63", pl->L);
+  if (pl->weighted) return fail(TEMX_EUNSUPPORTED, "latitude bins are not available on a weights-mode plan");
+  if (pl->finalized && pl->rank < pl->K)
+    return fail(TEMX_EUNSUPPORTED, "latitude bins: the plan was finalised through the pseudo-inverse (rank %d < K = %d; "
+                                   "fewer distinct latitudes than harmonics)", pl->rank, pl->K);
+  if (miss_mode(pl)) return fail(TEMX_EUNSUPPORTED, "latitude bins are not available in missing-value mode (TEMX_OPT_MISSING = 1)");
+  return TEMX_OK;
+}
+
+// Built at the first binned temx_plan_set_tem / operator call and again after a change of B or of the plan's basis: the
+// sorted rows and chunks, the coefficient tables and the two basis changes
+static int bin_setup(temx_plan* pl) {
+  if (!pl->finalized) return fail(TEMX_ESTATE, "plan not finalised");
+  if (int rc = bin_check(pl)) return rc;
+  const int B = pl->opt_lat_bins, K = pl->K;
+  if (pl->bin_built == B) return TEMX_OK;
+  const int J = bin_degree(pl->L, B), KP = (K + 15) / 16 * 16;
+  if (J == 0) return fail(TEMX_EINVAL, "TEMX_OPT_LAT_BINS: (L, B) = (%d, %d) is not served", pl->L, B);
+  BinRows br;
+  if (!build_bin_rows(pl->h_lat.data(), pl->N, B, br))
+    return fail(TEMX_EINVAL, "latitude bins: the native latitudes must be finite and lie in [-90, 90] degrees");
+  int rc;
+  if ((rc = upload(pl->bin_rows, br.rows))) return rc;
+  if ((rc = upload(pl->bin_s, br.s))) return rc;
+  if ((rc = upload(pl->bin_chunk, br.chunk))) return rc;
+  if ((rc = upload(pl->bin_c0, br.bin_chunk0))) return rc;
+  if ((rc = upload(pl->bin_a, bin_coefficients(pl->L, B, J, KP)))) return rc;
+  std::vector<double> TT((size_t)2 * KP * KP, 0.0);
+  for (int l = 0; l < K; ++l)
+    for (int j = 0; j < K; ++j) {
+      const double t = pl->qbasis ? pl->h_T[(size_t)l * K + j] : (l == j ? 1.0 : 0.0);   // Q_j = sum_l Y_l T[l][j]
+      TT[(size_t)j * KP + l] = t;                          // sums: B_Q[j] = sum_l T[l][j] B_Y[l]
+      TT[(size_t)KP * KP + (size_t)l * KP + j] = t;        // coefficients: c_Y[l] = sum_j T[l][j] c_Q[j]
+    }
+  if ((rc = upload(pl->bin_T, TT))) return rc;
+  pl->bin_J = J;
+  pl->bin_KP = KP;
+  pl->bin_nchunk = br.nchunk();
+  pl->bin_built = B;
+  return TEMX_OK;
+}
+
+// workspace of a binned run over D columns of NF fields; TEMX_ENOMEM with the byte count when it does not fit
+static int bin_workspace(temx_plan* pl, int64_t D, int NF) {
+  const int64_t Dpad = (D + 63) / 64 * 64;
+  const size_t need_cm = (size_t)pl->bin_nchunk * NF * pl->bin_J * Dpad * 8;
+  const size_t need_z = (size_t)pl->opt_lat_bins * NF * pl->bin_J * Dpad * 8;
+  const size_t need_cy = (size_t)NF * pl->K * D * 8;
+  const size_t need_p = (size_t)BIN_SLABS * NF * pl->K * D * 8;
+  size_t more = 0;
+  const DevBuf* bufs[4] = {&pl->bin_cm, &pl->bin_z, &pl->bin_cy, &pl->partial};
+  const size_t needs[4] = {need_cm, need_z, need_cy, need_p};
+  for (int i = 0; i < 4; ++i)
+    if (bufs[i]->bytes < needs[i]) more += needs[i];
+  size_t fr = 0, tot = 0;
+  if (more && hipMemGetInfo(&fr, &tot) == hipSuccess && more > fr)
+    return fail(TEMX_ENOMEM, "latitude bins: the workspace of the binned sweeps needs %zu more bytes (chunk moments %zu, series %zu), "
+                             "%zu are free; process the snapshots in smaller blocks", more, need_cm, need_z, fr);
+  int rc;
+  if ((rc = pl->bin_cm.ensure(need_cm))) return rc;
+  if ((rc = pl->bin_z.ensure(need_z))) return rc;
+  if ((rc = pl->bin_cy.ensure(need_cy))) return rc;
+  return pl->partial.ensure(std::max(need_p, pl->partial.bytes));
+}
+
+static int bin_set_tem(temx_plan* pl) {
+  if (int rc = bin_setup(pl)) return rc;
+  return bin_workspace(pl, pl->D, 4);
+}
+
+// chunk moments of NF fields -> raw sums B[NF][K][D] in the plan's projection basis
+static int bin_contract(temx_plan* pl, int NF, int64_t D, double* B, hipStream_t st) {
+  const int Dw = (int)((D + 63) / 64);
+  const int* c0 = static_cast<const int*>(pl->bin_c0.p);
+  const dim3 grid((unsigned)Dw, (unsigned)NF, BIN_SLABS);
+#define TEMX_LBC(KPv)                                                                                                  \
+  hipLaunchKernelGGL(bin_contract_kernel<KPv>, grid, dim3(64), 0, st, pl->bin_cm.d(), NF, pl->bin_J, D, Dw, pl->opt_lat_bins, \
+                     pl->K, c0, pl->bin_a.d(), pl->partial.d())
+  TEMX_BIN_KP(TEMX_LBC)
+#undef TEMX_LBC
+  HIPCHK(hipGetLastError());
+  int rc;
+  if ((rc = launch_reduce(pl, pl->partial.d(), BIN_SLABS, (int64_t)NF * pl->K * D, B, st))) return rc;
+  if (!pl->qbasis) return TEMX_OK;
+  const dim3 gb((unsigned)Dw, (unsigned)NF);
+#define TEMX_LBB(KPv) \
+  hipLaunchKernelGGL(bin_basis_kernel<KPv>, gb, dim3(64), 0, st, B, (int64_t)pl->K, pl->bin_T.d(), pl->K, D, B, (int64_t)pl->K)
+  TEMX_BIN_KP(TEMX_LBB)
+#undef TEMX_LBB
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+// coefficients C[NF][K4][D] in the plan's basis -> the per-bin Chebyshev series z[B][NF][J][Dpad] of the native means
+static int bin_synth(temx_plan* pl, int NF, int64_t D, const double* C, hipStream_t st) {
+  const int Dw = (int)((D + 63) / 64);
+  const int* c0 = static_cast<const int*>(pl->bin_c0.p);
+  const double* Tc = pl->bin_T.d() + (size_t)pl->bin_KP * pl->bin_KP;
+  const dim3 gb((unsigned)Dw, (unsigned)NF), grid((unsigned)Dw, (unsigned)NF, BIN_SLABS);
+#define TEMX_LBS(KPv)                                                                                                  \
+  do {                                                                                                                 \
+    hipLaunchKernelGGL(bin_basis_kernel<KPv>, gb, dim3(64), 0, st, C, (int64_t)pl->K4, Tc, pl->K, D, pl->bin_cy.d(), (int64_t)pl->K); \
+    hipLaunchKernelGGL(bin_synth_kernel<KPv>, grid, dim3(64), 0, st, pl->bin_cy.d(), NF, pl->bin_J, D, Dw, pl->opt_lat_bins, \
+                       pl->K, c0, pl->bin_a.d(), pl->bin_z.d());                                                       \
+  } while (0)
+  TEMX_BIN_KP(TEMX_LBS)
+#undef TEMX_LBS
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+// temx_tem_run with latitude bins: two reads of the four fields; B4, C4, the zonal means and the validity flags are
+// left as the generic two-pass stages leave them, so that the eddies and the tracers run their own kernels afterwards
+static int bin_tem_run(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double* results, double* zonal, hipStream_t st) {
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  int rc;
+  if ((rc = bin_setup(pl))) return rc;
+  const int64_t D = pl->D;
+  if ((rc = bin_workspace(pl, D, 4))) return rc;
+  set_tail(pl, 0, pl->nt);
+  pl->op_valid = pl->os_valid = pl->c4_valid = pl->tq_valid = false;
+  TimedLaunch tl{};
+  time_begin(pl, 0, st, tl);
+  rc = launch_bin_moments<4>(pl, fp, dtype, D, pl->colscale.d(), 2, st);
+  time_end(pl, 0, st, tl);
+  if (rc) return rc;
+  if ((rc = bin_contract(pl, 4, D, pl->B4.d(), st))) return rc;
+  // C = G^-1 B4 and the four zonal means ub vb thetab wapb -> zb[0..3]
+  if ((rc = launch_solve(pl, pl->B4.d(), 4, D, pl->C4.d(), pl->zb.d(), st))) return rc;
+  pl->c4_valid = true;
+  if ((rc = bin_synth(pl, 4, D, pl->C4.d(), st))) return rc;
+  const int Dw = (int)((D + 63) / 64);
+  const dim3 grid = bin_sweep_grid(pl, D);
+  const int4* ch = static_cast<const int4*>(pl->bin_chunk.p);
+  const int* rows = static_cast<const int*>(pl->bin_rows.p);
+  TimedLaunch tl2{};
+  time_begin(pl, 1, st, tl2);
+#define TEMX_LBE(Jv)                                                                                                   \
+  do {                                                                                                                 \
+    if (dtype == TEMX_F64)                                                                                             \
+      hipLaunchKernelGGL((bin_eddy_moments_kernel<double, Jv>), grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), \
+                         pl->colscale.d(), pl->bin_z.d(), pl->bin_cm.d());                                             \
+    else                                                                                                               \
+      hipLaunchKernelGGL((bin_eddy_moments_kernel<float, Jv>), grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), \
+                         pl->colscale.d(), pl->bin_z.d(), pl->bin_cm.d());                                             \
+  } while (0)
+  TEMX_BIN_J(TEMX_LBE)
+#undef TEMX_LBE
+  time_end(pl, 1, st, tl2);
+  HIPCHK(hipGetLastError());
+  if ((rc = bin_contract(pl, 3, D, pl->B3.d(), st))) return rc;
+  return tem_stage3_impl(pl, pl->B3.d(), results, zonal, st);
+}
+
+// temx_project with latitude bins
+static int bin_project_op(temx_plan* pl, const void* A, int dtype, int64_t D, double* B, hipStream_t st) {
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  int rc;
+  if ((rc = bin_setup(pl))) return rc;
+  if ((rc = bin_workspace(pl, D, 1))) return rc;
+  FieldPtrs<1> fp;
+  fp.p[0] = A;
+  if ((rc = launch_bin_moments<1>(pl, fp, dtype, D, nullptr, -1, st))) return rc;
+  return bin_contract(pl, 1, D, B, st);
+}
+
+// temx_zonal_mean with latitude bins: the binned projection, the plan's solve, and for the native mean the per-bin
+// series evaluated at every column
+static int bin_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* out, int native, hipStream_t st) {
+  if (D < 1 || D >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "D must be in [1, 2^28)");
+  HIPCHK(hipSetDevice(pl->device));
+  int rc;
+  if ((rc = pl->opB.ensure((size_t)pl->K * D * 8))) return rc;
+  if ((rc = bin_project_op(pl, A, dtype, D, pl->opB.d(), st))) return rc;
+  if (!native) return launch_solve(pl, pl->opB.d(), 1, D, nullptr, out, st);
+  if ((rc = pl->opC.ensure((size_t)pl->K4 * D * 8))) return rc;
+  if ((rc = launch_solve(pl, pl->opB.d(), 1, D, pl->opC.d(), nullptr, st))) return rc;
+  if ((rc = bin_synth(pl, 1, D, pl->opC.d(), st))) return rc;
+  const int Dw = (int)((D + 63) / 64);
+  const int4* ch = static_cast<const int4*>(pl->bin_chunk.p);
+  const int* rows = static_cast<const int*>(pl->bin_rows.p);
+#define TEMX_LBN(Jv) \
+  hipLaunchKernelGGL(bin_native_kernel<Jv>, bin_sweep_grid(pl, D), dim3(256), 0, st, D, Dw, ch, rows, pl->bin_s.d(), pl->bin_z.d(), out)
+  TEMX_BIN_J(TEMX_LBN)
+#undef TEMX_LBN
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
 int temx_tem_run(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                  int dtype, double* results, double* zonal, void* stream) try {
   int rc = tem_ready(pl);
@@ -3034,6 +3342,11 @@ int temx_tem_run(temx_plan* pl, const void* ua, const void* va, const void* ta, 
     if (!ua || !va || !ta || !wap || !results) return fail(TEMX_EINVAL, "null argument");
     HIPCHK(hipSetDevice(pl->device));
     return miss_tem_run(pl, four(ua, va, ta, wap), dtype, results, zonal, S_(stream));
+  }
+  if (bin_mode(pl)) {
+    if (!ua || !va || !ta || !wap || !results) return fail(TEMX_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(pl->device));
+    return bin_tem_run(pl, four(ua, va, ta, wap), dtype, results, zonal, S_(stream));
   }
   if (os_active(pl, dtype)) {
     if ((rc = os_ready(pl))) return rc;
@@ -3122,6 +3435,7 @@ static int tracer_ws(temx_plan* pl) {
 
 int temx_tracer_stage1(temx_plan* pl, const void* q, int dtype, double* Bq, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage1");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tracer_stage1");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!q || !Bq) return fail(TEMX_EINVAL, "null argument");
@@ -3142,6 +3456,7 @@ int temx_tracer_stage1(temx_plan* pl, const void* q, int dtype, double* Bq, void
 int temx_tracer_stage2(temx_plan* pl, const void* q, const void* va, const void* wap, int dtype,
                        const double* Bq, double* Bq2, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage2");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tracer_stage2");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!q || !va || !wap || !Bq || !Bq2) return fail(TEMX_EINVAL, "null argument");
@@ -3177,6 +3492,7 @@ int temx_tracer_stage2(temx_plan* pl, const void* q, const void* va, const void*
 
 int temx_tracer_stage3(temx_plan* pl, const double* Bq2, double* tres, double* tzon, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage3");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tracer_stage3");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!Bq2 || !tres) return fail(TEMX_EINVAL, "null argument");
@@ -3205,6 +3521,7 @@ static inline bool tracer_one_pass(const temx_plan* pl) { return pl->cls && pl->
 int temx_tracer_stage1_sums(temx_plan* pl, const void* q, const void* va, const void* wap, int dtype,
                             double* Bq, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage1_sums");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tracer_stage1_sums");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!q || !va || !wap || !Bq) return fail(TEMX_EINVAL, "null argument");
@@ -3229,6 +3546,7 @@ int temx_tracer_stage1_sums(temx_plan* pl, const void* q, const void* va, const 
 
 int temx_tracer_stage2_from_sums(temx_plan* pl, const double* Bq, double* Bq2, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tracer_stage2_from_sums");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tracer_stage2_from_sums");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!Bq || !Bq2) return fail(TEMX_EINVAL, "null argument");
@@ -3257,6 +3575,7 @@ int temx_tracer_stage2_from_sums(temx_plan* pl, const double* Bq, double* Bq2, v
 int temx_tem_tracer_stage1(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
                            const void* q, int dtype, double* B4, double* Bq, void* stream) try {
   if (pl && miss_mode(pl)) return miss_refuse("temx_tem_tracer_stage1");
+  if (pl && bin_refused(pl)) return bin_refuse("temx_tem_tracer_stage1");
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !q || !B4 || !Bq) return fail(TEMX_EINVAL, "null argument");
@@ -3327,6 +3646,7 @@ int temx_tracer_run(temx_plan* pl, const void* q, const void* va, const void* wa
     return tracer_run_os(pl, 1, qs, va, wap, dtype, tr, tz, stream);
   }
   if ((rc = tracer_ws(pl))) return rc;
+  BinPass through_stages(pl);      // latitude bins: the tracer's stages are the plan's own two-pass kernels, unchanged
   // The one-pass form reads (q, v, omega) once instead of q + (q, v, omega), but its sweep shares a SIMD
   // with fewer waves than the two-pass kernels: measured on ne120 x 72 x 30 it is no faster (10.2 ms
   // against 9.6 ms), so the two-pass stages stay the default and TEMX_TRACER_ONE_PASS=1 selects it.

@@ -23,11 +23,23 @@ def _dbl(a):
     return a, a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def lat_bins_value(lat_bins):
+    """The TEMX_OPT_LAT_BINS value of a ``lat_bins`` argument: ``True`` -> -1 (the library's default), 0 / ``False`` /
+    ``None`` -> 0, one of the allowed bin counts -> itself; anything else raises ValueError (no device needed)."""
+    if lat_bins is None or lat_bins is False:
+        return 0
+    if lat_bins is True:
+        return -1
+    if isinstance(lat_bins, (int, np.integer)) and (int(lat_bins) == 0 or int(lat_bins) in _lib.LAT_BINS_ALLOWED):
+        return int(lat_bins)
+    raise ValueError("lat_bins must be True, 0 or one of %s, got %r" % (_lib.LAT_BINS_ALLOWED, lat_bins))
+
+
 class Plan:
     """One plan per (device, native grid, output latitudes, L).  See include/temx.h."""
 
     def __init__(self, lat_deg, lat_out_deg, L, device=0, defer_finalize=False, symmetry=True, classes=True, qr=True,
-                 form=None, fp32_fields=False):
+                 form=None, fp32_fields=False, lat_bins=None):
         self._h = C.c_void_p()
         self.lib = _lib.load()
         if isinstance(device, torch.device):
@@ -48,6 +60,8 @@ class Plan:
                                         | (_lib.LAT_TOL_F32 if fp32_fields else 0)))
         if form is not None:
             self.configure(form=form)
+        if lat_bins is not None:
+            self.configure(lat_bins=lat_bins)
 
     @property
     def paired(self):
@@ -78,7 +92,7 @@ class Plan:
 
     def configure(self, form=None, os_map=None, op_map=None, os_subsample=None, tracer_one_pass=None,
                   single_sweep_min_groups=None, os_contract=None, missing=None, min_coverage=None,
-                  missing_weight=None, os_sync=None):
+                  missing_weight=None, os_sync=None, lat_bins=None):
         """Path selection (temx_plan_configure); ``set_tem`` must follow.  ``form``: a key of ``_lib.FORMS``
         ("auto", "two-pass", "class-sums", "single-sweep", "no-single-sweep"); ``os_map`` / ``op_map``:
         "row" or "tile" (lane map of the loads of the single sweep / of sweep 1 of the class-sum form).
@@ -86,7 +100,10 @@ class Plan:
         (include/temx.h, missing-value mode); ``min_coverage`` in [0, 1] (outputs whose coverage is below it are
         NaN, 0 disables; default 0.5); ``missing_weight`` tau, a power of ten in [1e-14, 1e-4] (default 1e-10).
         ``os_sync``: "flags" (default) or "barrier" -- how the waves of the single sweep of fp64 fields hand a
-        class-group's sums over (same bits; A/B)."""
+        class-group's sums over (same bits; A/B).
+        ``lat_bins``: ``True`` (the library's default number of latitude bins), an int in {128, 256, 512, 1024, 2048},
+        or 0 / ``False`` (off, the default) -- the opt-in latitude-bin form of ``tem_run``, ``project`` and
+        ``zonal_mean`` for grids without repeated latitudes (include/temx.h, latitude-bin form)."""
         def put(opt, val):
             check(self.lib.temx_plan_configure(self._h, opt, int(val)))
         if missing is not None:
@@ -117,12 +134,29 @@ class Plan:
             put(_lib.OPT_SINGLE_SWEEP_MIN_GROUPS, single_sweep_min_groups)
         if os_contract is not None:     # "mfma" (default) or "lds" (the round-3 form, A/B)
             put(_lib.OPT_OS_CONTRACT, {"mfma": 0, "lds": 1}[os_contract] if isinstance(os_contract, str) else os_contract)
+        if lat_bins is not None:
+            put(_lib.OPT_LAT_BINS, lat_bins_value(lat_bins))
         if os_sync is not None:
             put(_lib.OPT_OS_SYNC, {"flags": 0, "barrier": 1}[os_sync] if isinstance(os_sync, str) else os_sync)
         self.nlev = self.nt = self.D = None
 
     def option(self, opt):
         return int(self.lib.temx_plan_option(self._h, int(opt)))
+
+    @property
+    def lat_bins(self):
+        """Number of latitude bins in effect, 0 when the latitude-bin form is off."""
+        return self.option(_lib.OPT_LAT_BINS)
+
+    @property
+    def bin_degree(self):
+        """Chebyshev terms per latitude bin the library chose for (L, bins); 0 when the form is off."""
+        return self.option(_lib.OPT_BIN_DEGREE)
+
+    @property
+    def sweep_form(self):
+        """What ``tem_run`` runs: "binned", "masked", "single-sweep", "class-sums" or "two-pass"."""
+        return _lib.FORM_NAMES.get(self.option(_lib.OPT_FORM), "two-pass")
 
     @property
     def missing(self):

@@ -124,6 +124,10 @@ class NcolShardedTEM:
             raise NotImplementedError("NcolShardedTEM: missing-value mode (missing='mask') needs the whole grid in one "
                                       "plan (the masked systems are per column of the zonal sums); use TimeShardedTEM "
                                       "or one plan per process")
+        if getattr(backend, "lat_bins", 0):
+            raise NotImplementedError("NcolShardedTEM: the latitude-bin form (lat_bins=) refuses the staged entry points "
+                                      "the ncol-sharded runners exchange sums through; use TimeShardedTEM or one plan "
+                                      "per process")
         self.backend = backend
         self.group = group
         self.world = _world(group)

@@ -45,7 +45,7 @@ class sph_zonal_averager:
 
     def __init__(self, lat, lat_out, L, weights=None, grid_name=None, grid_out_name=None,
                  ncoldim="ncol", overwrite=False, save_dest=None, debug=False, logfile=None,
-                 device=None, fp32_fields=False, missing="raise", min_coverage=0.5):
+                 device=None, fp32_fields=False, missing="raise", min_coverage=0.5, *, lat_bins=None):
         self.L = L
         # (not in the reference's signature) missing="mask": non-finite values are missing points of a masked fit
         # instead of an error; outputs whose coverage is below min_coverage are NaN (include/temx.h)
@@ -55,6 +55,13 @@ class sph_zonal_averager:
             raise ValueError("min_coverage must lie in [0, 1], got %r" % (min_coverage,))
         self.missing = missing
         self.min_coverage = float(min_coverage)
+        # (not in the reference's signature) lat_bins=True / a bin count: the opt-in latitude-bin form of the sweeps for
+        # grids without repeated latitudes (include/temx.h)
+        from . import engine
+        self._lat_bins = engine.lat_bins_value(lat_bins)
+        if self._lat_bins and missing == "mask":
+            raise ValueError("lat_bins and missing='mask' exclude each other: the latitude-bin form does not serve "
+                             "masked fields")
         # (not in the reference's signature) the arrays to be averaged are fp32: latitudes that agree to 1e-8 degrees
         # share a basis row (include/temx.h, TEMX_LAT_TOL_F32)
         self._fp32_fields = bool(fp32_fields)
@@ -94,6 +101,13 @@ class sph_zonal_averager:
         # scale grid weights to unit sphere surface area (:180-181); not in place
         if self._w_raw is not None:
             self.weights = self._w_raw * (4 * np.pi)
+
+    @property
+    def lat_bins(self):
+        """Number of latitude bins in effect (512 for ``lat_bins=True``), 0 when the latitude-bin form is off."""
+        if self._plan is not None:
+            return self._plan.lat_bins
+        return _lib.LAT_BINS_DEFAULT if self._lat_bins < 0 else self._lat_bins
 
     # ---- matrices (attributes Y0, Y0inv, Y0p of the reference, fetched lazily from the device) ----
     def _matrix(self, which):
@@ -170,6 +184,8 @@ class sph_zonal_averager:
             self._plan.set_weights(self._w_raw)
         if self.missing == "mask":
             self._plan.configure(missing="mask", min_coverage=self.min_coverage)
+        if self._lat_bins:
+            self._plan.configure(lat_bins=self._lat_bins if self._lat_bins > 0 else True)
         if cached is not None:
             # the engine applies its own factorisation of the same operator (built above for THIS grid, L and
             # weights); a cache is accepted only if it describes them too.  Quadrature weights do not make

@@ -40,7 +40,8 @@ class TEMDiagnostics:
     def __init__(self, ua, va, ta, wap, lat_native, q=None, p0=P0, zm_dlat=1, L=50,
                  dim_names=DEFAULT_DIMS, grid_name=None, zm_grid_name=None, map_save_dest=None,
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
-                 *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None):
+                 *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
+                 lat_bins=None):
         # ---- blocked run over the time axis (not in the reference): checked before anything touches the device ----
         self.time_block = layout.check_time_block(time_block)
         self._given_source = getattr(_pending, "source", None)
@@ -54,6 +55,8 @@ class TEMDiagnostics:
             self._refuse_masked_tracers()
         self.missing = missing
         self.min_coverage = float(min_coverage)
+        # ---- latitude-bin form (not in the reference; opt-in, include/temx.h): checked before anything touches the device
+        self._check_lat_bins(lat_bins, missing)
         # ---- arguments (tem_diagnostics.py:217-236) ----
         self.p0 = p0
         self.q = q
@@ -81,7 +84,7 @@ class TEMDiagnostics:
                                      grid_out_name=zm_grid_name, save_dest=map_save_dest,
                                      debug=debug_level > 1, overwrite=overwrite_map, device=self._device,
                                      fp32_fields=str(self._work_dtype) == "torch.float32",
-                                     missing=missing, min_coverage=self.min_coverage)
+                                     missing=missing, min_coverage=self.min_coverage, lat_bins=lat_bins)
         if self.ZM.Y0 is None or self.ZM.Y0p is None:
             self.ZM.sph_compute_matrices(overwrite=overwrite_map)
         self._zonal_mean = self.ZM.sph_zonal_mean
@@ -101,6 +104,27 @@ class TEMDiagnostics:
                 plan, self._dev_fields, self._dev_q, self.NT)
         else:
             self._run_blocked(plan)
+
+    @staticmethod
+    def _check_lat_bins(lat_bins, missing):
+        """The TEMX_OPT_LAT_BINS value of ``lat_bins`` (ValueError for a bad one, or next to ``missing="mask"``)."""
+        from . import engine
+        value = engine.lat_bins_value(lat_bins)
+        if value and missing == "mask":
+            raise ValueError("lat_bins and missing='mask' exclude each other: the latitude-bin form does not serve "
+                             "masked fields")
+        return value
+
+    @property
+    def lat_bins(self):
+        """Number of latitude bins the run used (512 for ``lat_bins=True``), 0 when the latitude-bin form is off."""
+        return self.ZM._plan.lat_bins
+
+    @property
+    def sweep_form(self):
+        """The form of the sweeps this object ran: "binned" (``lat_bins=``), "masked" (``missing="mask"``),
+        "single-sweep", "class-sums" or "two-pass"."""
+        return self.ZM._plan.sweep_form
 
     def _run_block(self, plan, fields, qs, nt):
         """One engine run over ``nt`` snapshots in engine layout (``plan.set_tem`` has been called for them):
@@ -242,6 +266,7 @@ class TEMDiagnostics:
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (kw["missing"],))
         if kw.get("missing", "raise") == "mask" and q is not None:
             cls._refuse_masked_tracers()
+        cls._check_lat_bins(kw.get("lat_bins"), kw.get("missing", "raise"))
         qs = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
         given = [ua, va, ta, wap] + qs
         if cls._model_level_order(given, kw.pop("dims", None), kw.get("dim_names", DEFAULT_DIMS)) == "time-major":
