@@ -4,6 +4,7 @@
 #include "../../include/temx_vert.h"
 #include "../../include/temx_layout.h"
 #include "../../include/temx_ingest.h"
+#include "../../include/temx_clim.h"
 
 #include <hip/hip_runtime.h>
 
@@ -33,9 +34,11 @@
 #include "kernels_vert.hpp"
 #include "kernels_layout.hpp"
 #include "kernels_ingest.hpp"
+#include "kernels_clim.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
 #include "bin_tables.hpp"
 #include "class_tables.hpp"
+#include "clim_shapes.hpp"
 #include "host_math.hpp"
 #include "launch_shapes.hpp"
 
@@ -1761,6 +1764,25 @@ static int launch_vert_nf(int nf, const void* const* src, void* const* dst, int6
   return launch_vert<T, VERT_NFMAX, HYB>(fp, nf, ncol, nlev, nt, nplev, tb, p0, P, p_f32, logp, hold, map, st);
 }
 
+// ---- the time sum (include/temx_clim.h): one launch for the sources of one dtype ----
+template <typename T>
+static int launch_time_sum(const ClimPtrs& fp, int nf, int64_t rows, int64_t nt, int accumulate, hipStream_t st) {
+  const ClimShape sh = clim_shape(rows, nt, sizeof(T));
+  if (sh.nblk >= (int64_t(1) << 32) / CLIM_THREADS)   // HIP takes fewer than 2^32 threads per grid dimension
+    return fail(TEMX_EUNSUPPORTED, "too many rows for one launch (%lld workgroups): sum the fields in parts", (long long)sh.nblk);
+  if (sh.staged) {
+    if ((size_t)sh.rpb * sh.stride * sizeof(T) > (size_t)CLIM_LDS_BYTES || (int64_t)sh.rpb * nt > (int64_t(1) << 30))
+      return fail(TEMX_EINTERNAL, "staged rows of the time sum exceed their LDS budget");
+    hipLaunchKernelGGL((time_sum_staged_kernel<T>), dim3((unsigned)sh.nblk, (unsigned)nf), dim3(CLIM_THREADS), 0, st, fp, rows,
+                       (int)nt, sh, accumulate);
+  } else {
+    hipLaunchKernelGGL((time_sum_long_kernel<T>), dim3((unsigned)sh.nblk, (unsigned)nf), dim3(CLIM_THREADS), 0, st, fp, rows, nt,
+                       accumulate);
+  }
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
 extern "C" {
 
 int temx_version(void) { return 402; }
@@ -2875,30 +2897,35 @@ static int tem_stage3_impl(temx_plan* pl, const double* B3, double* results, dou
   return tem_epilogue(pl, results, zonal, st);
 }
 
-// int_vbdp, derivatives, psi and the ten diagnostics from the seven zonal means in zb[0..6]
-static int tem_epilogue(temx_plan* pl, double* results, double* zonal, hipStream_t st) {
-  const int64_t Dt = pl->tD, nts = pl->tnt;
+// int_vbdp, derivatives, psi and the ten diagnostics from the seven zonal means in zb[0..6], [8][M][nlev][nts]: the
+// plan's own buffer (tem_epilogue) or the caller's (temxc_tem_from_zonal_means); reads the plan's tables only
+static int tem_epilogue_on(temx_plan* pl, double* zb, int64_t nts, double* results, double* zonal, hipStream_t st) {
+  const int64_t Dt = (int64_t)pl->nlev * nts;
   const int64_t MD = (int64_t)pl->M * Dt;
   // int_vbdp -> zb[7]: by a wavefront scan; inside the epilogue only for short columns on small zonal grids
   // (measured: at nlev = 72 the O(nlev) loop per point costs what the extra launch saves, at 128 more)
   EpiTables tb{pl->p.d(), pl->pg.d(), pl->lg.d(), pl->coslat.d(), pl->fcor.d()};
   static const bool epi_wg = !(getenv("TEMX_EPI_WG") && atoi(getenv("TEMX_EPI_WG")) == 0);   // A/B only
   if (epi_wg && Dt <= EPI_WG_MAXD) {          // small zonal grid: the scan inside the epilogue, one workgroup per latitude
-    hipLaunchKernelGGL(tem_epilogue_kernel<2>, dim3((unsigned)pl->M), dim3(256), 0, st, pl->zb.d(), pl->M, pl->nlev, nts, tb,
+    hipLaunchKernelGGL(tem_epilogue_kernel<2>, dim3((unsigned)pl->M), dim3(256), 0, st, zb, pl->M, pl->nlev, nts, tb,
                        pl->p0, results, zonal);
   } else if (pl->nlev > 40 || MD > ((int64_t)1 << 17)) {
     const int64_t ncols = (int64_t)pl->M * nts;
-    hipLaunchKernelGGL(pint_scan_kernel, dim3((unsigned)((ncols + 3) / 4)), dim3(256), 0, st, pl->zb.d() + 1 * MD,
-                       pl->p.d(), pl->M, pl->nlev, nts, pl->zb.d() + 7 * MD);
+    hipLaunchKernelGGL(pint_scan_kernel, dim3((unsigned)((ncols + 3) / 4)), dim3(256), 0, st, zb + 1 * MD,
+                       pl->p.d(), pl->M, pl->nlev, nts, zb + 7 * MD);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(tem_epilogue_kernel<0>, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, pl->zb.d(),
+    hipLaunchKernelGGL(tem_epilogue_kernel<0>, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, zb,
                        pl->M, pl->nlev, nts, tb, pl->p0, results, zonal);
   } else {
-    hipLaunchKernelGGL(tem_epilogue_kernel<1>, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, pl->zb.d(),
+    hipLaunchKernelGGL(tem_epilogue_kernel<1>, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, zb,
                        pl->M, pl->nlev, nts, tb, pl->p0, results, zonal);
   }
   HIPCHK(hipGetLastError());
   return TEMX_OK;
+}
+
+static int tem_epilogue(temx_plan* pl, double* results, double* zonal, hipStream_t st) {
+  return tem_epilogue_on(pl, pl->zb.d(), pl->tnt, results, zonal, st);
 }
 
 // ---- the single sweep in three steps (ncol-sharded jobs exchange between them; see include/temx.h) -----------
@@ -4074,6 +4101,72 @@ int temxi_records_to_pressure(int device, int nf, const void* const* src_host, c
 #undef TEMXI_GO
   HIPCHK(hipGetLastError());
   return TEMX_OK;
+} TEMX_CATCH
+
+// ---- time-mean TEM: the sum over time and the epilogue on the caller's zonal means (include/temx_clim.h) ----
+int temxc_version(void) { return 100; }
+
+int temxc_time_sum(int device, int nf, const void* const* src_host, const int* src_dtype_host, double* const* acc_host,
+                   int64_t ncol, int nlev, int64_t nt, int flags, void* stream) try {
+  if (nf < 1 || nf > TEMXC_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", (int)TEMXC_NF_MAX, nf);
+  if (!src_host) return fail(TEMX_EINVAL, "src_host is null");
+  if (!src_dtype_host) return fail(TEMX_EINVAL, "src_dtype_host is null");
+  if (!acc_host) return fail(TEMX_EINVAL, "acc_host is null");
+  if (ncol < 1) return fail(TEMX_EINVAL, "ncol must be at least 1");
+  if (nlev < 1) return fail(TEMX_EINVAL, "nlev must be at least 1");
+  if (nt < 1) return fail(TEMX_EINVAL, "nt must be at least 1");
+  if (nlev > (1 << 20) || nt > (int64_t(1) << 31) || ncol > (int64_t(1) << 40))
+    return fail(TEMX_EINVAL, "sizes out of range (ncol, nlev or nt)");
+  if ((double)ncol * (double)nlev * (double)nt > 281474976710656.0)
+    return fail(TEMX_EINVAL, "sizes out of range (ncol * nlev * nt above 2^48)");
+  if (flags & ~(int)TEMXC_ACCUMULATE) return fail(TEMX_EINVAL, "flags has unknown bits (0x%x)", (unsigned)flags);
+  const int64_t rows = ncol * nlev;
+  const size_t src_elems = (size_t)rows * nt, acc_bytes = (size_t)rows * sizeof(double);
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+  };
+  for (int f = 0; f < nf; ++f) {
+    if (src_dtype_host[f] != TEMX_F64 && src_dtype_host[f] != TEMX_F32)
+      return fail(TEMX_EINVAL, "src_dtype %d must be TEMX_F64 or TEMX_F32", f);
+    if (!src_host[f]) return fail(TEMX_EINVAL, "src %d is null", f);
+    if (!acc_host[f]) return fail(TEMX_EINVAL, "acc %d is null", f);
+    if ((uintptr_t)src_host[f] % (src_dtype_host[f] == TEMX_F64 ? 8 : 4))
+      return fail(TEMX_EINVAL, "src %d is not aligned to its element size", f);
+    if ((uintptr_t)acc_host[f] % sizeof(double)) return fail(TEMX_EINVAL, "acc %d is not aligned to its element size", f);
+  }
+  for (int f = 0; f < nf; ++f)
+    for (int g = 0; g < nf; ++g) {
+      if (overlap(acc_host[f], acc_bytes, src_host[g], src_elems * (src_dtype_host[g] == TEMX_F64 ? 8 : 4)))
+        return fail(TEMX_EINVAL, "acc %d overlaps src %d", f, g);
+      if (g < f && overlap(acc_host[f], acc_bytes, acc_host[g], acc_bytes))
+        return fail(TEMX_EINVAL, "acc %d overlaps acc %d", f, g);
+    }
+  // the fp64 and the fp32 sources go in a launch each: their rows are cut differently (clim_shapes.hpp)
+  ClimPtrs p64{}, p32{};
+  int n64 = 0, n32 = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (src_dtype_host[f] == TEMX_F64) p64.src[n64] = src_host[f], p64.acc[n64++] = acc_host[f];
+    else p32.src[n32] = src_host[f], p32.acc[n32++] = acc_host[f];
+  }
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = S_(stream);
+  const int accumulate = (flags & TEMXC_ACCUMULATE) ? 1 : 0;
+  int rc;
+  if (n64 && (rc = launch_time_sum<double>(p64, n64, rows, nt, accumulate, st))) return rc;
+  if (n32 && (rc = launch_time_sum<float>(p32, n32, rows, nt, accumulate, st))) return rc;
+  return TEMX_OK;
+} TEMX_CATCH
+
+int temxc_tem_from_zonal_means(temx_plan* pl, double* zm8, int64_t nts, double* results, double* zonal, void* stream) try {
+  int rc = tem_ready(pl);
+  if (rc) return rc;
+  if (!zm8 || !results) return fail(TEMX_EINVAL, "null argument");
+  if (nts < 1) return fail(TEMX_EINVAL, "nts must be at least 1");
+  if ((double)pl->M * (double)pl->nlev * (double)nts >= 2147483648.0)
+    return fail(TEMX_EUNSUPPORTED, "M * nlev * nts = %.0f is too large for one launch", (double)pl->M * pl->nlev * (double)nts);
+  HIPCHK(hipSetDevice(pl->device));
+  return tem_epilogue_on(pl, zm8, nts, results, zonal, S_(stream));
 } TEMX_CATCH
 
 }  // extern "C"

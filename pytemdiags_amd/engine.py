@@ -572,6 +572,74 @@ class Plan:
         check(self.lib.temx_tracer_eddy(self._h, _ptr(qq), _ptr(v), _ptr(w), dt, ptrs, self._stream()))
         return outs
 
+    # ---- time-mean TEM (include/temx_clim.h) ----
+    def time_sum(self, fields, acc=None, accumulate=False):
+        """Sum over the last (time) axis of up to eight contiguous device tensors ``[ncol][nlev][nt]``, fp64 or fp32
+        each (temxc_time_sum): -> a list of fp64 ``[ncol][nlev]`` tensors, ``acc`` itself when given (``+=`` under
+        ``accumulate``).  Every addition is fp64; the sum of a row depends on its values, ``nt`` and dtype only."""
+        from . import _clim
+        lib = _clim.load()
+        fields = list(fields)
+        if not 1 <= len(fields) <= _clim.NF_MAX:
+            raise ValueError("time_sum takes 1..%d fields, got %d" % (_clim.NF_MAX, len(fields)))
+        shape = tuple(fields[0].shape)
+        if len(shape) != 3:
+            raise ValueError("fields must be [ncol][nlev][nt], got %d dims" % len(shape))
+        fs = []
+        for x in fields:
+            if not isinstance(x, torch.Tensor):
+                raise TypeError("device tensors expected")
+            if x.device != self.device:
+                raise ValueError("tensor on %s, plan on %s" % (x.device, self.device))
+            if x.dtype not in _DT:
+                raise TypeError("dtype must be float64 or float32, got %s" % x.dtype)
+            if tuple(x.shape) != shape:
+                raise ValueError("field has shape %s, expected %s" % (tuple(x.shape), shape))
+            fs.append(x.contiguous())
+        if acc is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs acc=")
+            acc = list(torch.empty((len(fs),) + shape[:2], dtype=torch.float64, device=self.device).unbind(0))
+        acc = list(acc)
+        if len(acc) != len(fs):
+            raise ValueError("acc has %d tensors for %d fields" % (len(acc), len(fs)))
+        for a in acc:
+            if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float64
+                    and tuple(a.shape) == shape[:2] and a.is_contiguous()):
+                raise ValueError("acc must hold contiguous float64 [ncol][nlev] tensors on the plan's device")
+        n = len(fs)
+        src = (C.c_void_p * n)(*[x.data_ptr() for x in fs])
+        sdt = (C.c_int * n)(*[_DT[x.dtype] for x in fs])
+        dst = (C.c_void_p * n)(*[a.data_ptr() for a in acc])
+        check(lib.temxc_time_sum(self.device_index, n, src, sdt, dst, shape[0], shape[1], shape[2],
+                                 _clim.ACCUMULATE if accumulate else 0, self._stream()))
+        return acc
+
+    def tem_from_zonal_means(self, zm7, want_zonal=False):
+        """The epilogue of a TEM run on zonal means the caller supplies (temxc_tem_from_zonal_means): ``zm7`` is
+        ``[7][M][nlev][nts]`` fp64 in the order ``ub vb thetab wapb upvpb upwappb vptpb``, ``nts`` any value >= 1.
+        -> (results ``[10][M][nlev][nts]``, zonal intermediates ``[16][M][nlev][nts]`` or None).  Needs ``set_tem``;
+        leaves the plan as it found it."""
+        from . import _clim
+        lib = _clim.load()
+        if self.D is None:
+            raise _lib.TemxError(-5, "temx_plan_set_tem has not been called")
+        if not isinstance(zm7, torch.Tensor) or zm7.device != self.device or zm7.dtype != torch.float64:
+            raise TypeError("zm7 must be a float64 tensor on the plan's device")
+        if zm7.dim() != 4 or zm7.shape[0] != 7 or zm7.shape[1] != self.M or zm7.shape[2] != self.nlev or zm7.shape[3] < 1:
+            raise ValueError("zm7 must be [7][%d][%d][nts], got %s" % (self.M, self.nlev, tuple(zm7.shape)))
+        nts = int(zm7.shape[3])
+        zm8 = torch.empty((8, self.M, self.nlev, nts), dtype=torch.float64, device=self.device)
+        zm8[:7] = zm7
+        zm8[7] = 0
+        res = torch.empty((len(_lib.RESULT_NAMES), self.M, self.nlev, nts), dtype=torch.float64, device=self.device)
+        zon = None
+        if want_zonal:
+            zon = torch.empty((len(_lib.ZONAL_NAMES), self.M, self.nlev, nts), dtype=torch.float64, device=self.device)
+        check(lib.temxc_tem_from_zonal_means(self._h, _ptr(zm8), nts, _ptr(res), _ptr(zon) if zon is not None else None,
+                                             self._stream()))
+        return res, zon
+
     def status(self):
         """Synchronise; True when a non-finite value reached the zonal sums (NaN input)."""
         f = C.c_int(0)

@@ -20,6 +20,7 @@ import warnings
 import numpy as np
 
 from . import _lib, containers, layout
+from . import climatology as clim
 from .constants import P0, Om
 from .sph_zonal_mean import sph_zonal_averager
 
@@ -41,7 +42,10 @@ class TEMDiagnostics:
                  dim_names=DEFAULT_DIMS, grid_name=None, zm_grid_name=None, map_save_dest=None,
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
-                 lat_bins=None):
+                 lat_bins=None, climatology=False):
+        # ---- time-mean TEM (not in the reference; climatology.py): checked before anything touches the device ----
+        self._want_climatology = clim.check_flag(climatology, missing)
+        self._climatology = None
         # ---- blocked run over the time axis (not in the reference): checked before anything touches the device ----
         self.time_block = layout.check_time_block(time_block)
         self._given_source = getattr(_pending, "source", None)
@@ -98,12 +102,27 @@ class TEMDiagnostics:
         self._last_tracer = None
         self._after_launch = None
         self.block_timing = None
+        self._clim = clim.Builder(self, plan) if self._want_climatology else None
         if self.time_block is None and self._block_source is None:
+            if self._clim is not None:      # time means and their TEM first: the ordinary run is the plan's last
+                self._clim.add(self._dev_fields)
+                self._clim.run_stationary()
             plan.set_tem(self.NLEV, self.NT, self._p_np, float(self.p0))
             self._res, self._zon, self._cov, self._tres, self._tzon = self._run_block(
                 plan, self._dev_fields, self._dev_q, self.NT)
         else:
             self._run_blocked(plan)
+        if self._clim is not None:
+            self._climatology = self._clim.finish(self._zon)
+            self._clim = None
+
+    @property
+    def climatology(self):
+        """``climatology=True``: the time-mean TEM of the record with its stationary and transient parts, a
+        ``climatology.TEMClimatology`` (attributes ``total``, ``stationary``, ``transient``)."""
+        if self._climatology is None:
+            raise RuntimeError("climatology is not available: build the object with climatology=True")
+        return self._climatology
 
     @staticmethod
     def _check_lat_bins(lat_bins, missing):
@@ -181,6 +200,13 @@ class TEMDiagnostics:
             for n, (t0, t1) in enumerate(blocks):
                 ntb = t1 - t0
                 fs = src.get(n)
+                if self._clim is not None:
+                    # the time sum of the block, on the stream of its TEM run and before the source has it back
+                    self._clim.add(fs[:4])
+                    if self.time_block is None:
+                        # one block whose fields are kept: as in a whole run, the ordinary run is the plan's last
+                        self._clim.run_stationary()
+                        cur = None
                 if ntb != cur:
                     plan.set_tem(self.NLEV, ntb, self._p_np, float(self.p0))
                     cur = ntb
@@ -210,6 +236,8 @@ class TEMDiagnostics:
             src.close()
             self.block_timing = src.timing
             self._block_source = None
+        if self._clim is not None and self.time_block is not None:
+            self._clim.run_stationary()     # after the last block: a blocked run serves no native outputs
         self._res, self._zon, self._cov, self._tres, self._tzon = big
         self._last_tracer = None
 
@@ -267,6 +295,7 @@ class TEMDiagnostics:
         if kw.get("missing", "raise") == "mask" and q is not None:
             cls._refuse_masked_tracers()
         cls._check_lat_bins(kw.get("lat_bins"), kw.get("missing", "raise"))
+        clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"))
         qs = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
         given = [ua, va, ta, wap] + qs
         if cls._model_level_order(given, kw.pop("dims", None), kw.get("dim_names", DEFAULT_DIMS)) == "time-major":
@@ -591,8 +620,9 @@ class TEMDiagnostics:
             return np.result_type(*[self._np_dtype(v) for v in var]).type
         return {torch.float32: np.float32, torch.float64: np.float64}.get(self._in_dtype[var], np.float64)
 
-    def _wrap(self, t, name, src_var, native=False, force64=False):
-        """Label a device result; cast like the reference's astype."""
+    def _wrap(self, t, name, src_var, native=False, force64=False, time=None):
+        """Label a device result; cast like the reference's astype.  ``time``: the time coordinate when
+        it is not the input's (the time-mean results of ``climatology``)."""
         import torch
         dt = np.float64 if (force64 or name in _F64_ALWAYS) else self._np_dtype(src_var)
         dt = np.float64 if dt == np.float64 else np.float32
@@ -603,7 +633,7 @@ class TEMDiagnostics:
             return vals
         first = self.ncolname if native else "lat"
         dims = (first, self.plevname, self.timename)
-        coords = {self.plevname: self.plev, self.timename: self.time}
+        coords = {self.plevname: self.plev, self.timename: self.time if time is None else time}
         if not native:
             coords["lat"] = self._lat_zm
         return containers.make_like(self._kind, vals, dims, coords, name)
