@@ -50,9 +50,12 @@ enum { TEMXV_NF_MAX = 8 };
 int temxv_version(void); /* 100 */
 
 /* nf in 1..TEMXV_NF_MAX fields in one launch.  TEMX_EINVAL: nf out of range, a null pointer, sizes below 1
- * (nlev below 2), plev not strictly ascending or not positive, non-finite hyam / hybm / p0_hybrid, an unknown flag,
- * a pointer not aligned to its element size, a dst that overlaps a src or another dst.  hyam_host and hybm_host are
- * read in hybrid mode only (they may be NULL in field mode).  device is used as given.
+ * (nlev below 2) or out of range (nlev, nplev above 2^20, nt above 2^31, ncol above 2^40, or
+ * ncol * max(nlev, nplev) * nt above 2^48, as in temx_layout.h, temx_ingest.h and temx_clim.h), plev not strictly
+ * ascending or not positive, non-finite hyam / hybm / p0_hybrid, an unknown flag, a pointer not aligned to its element
+ * size, a dst that overlaps a src, ps_or_p or another dst.  An array that would end beyond the top of the address space
+ * is taken as reaching it in the overlap test, not as wrapping round.  hyam_host and hybm_host are read in hybrid mode
+ * only (they may be NULL in field mode).  device is used as given.
  * The lane map is chosen by row length (rows of nt * itemsize below 128 bytes take the slab-staged map);
  * TEMXV_MAP=time or TEMXV_MAP=slab in the environment overrides the choice for A/B runs. */
 int temxv_interp(int device, int nf,

@@ -27,8 +27,6 @@ SIGNATURES = [
     ("temxc_tem_from_zonal_means", _i, [_vp, _vp, _i64, _vp, _vp, _vp]),
 ]
 
-_bound = None
-
 
 def switch_nt(itemsize):
     """The smallest ``nt`` whose rows take the long-row kernel of the time sum, for sources of ``itemsize`` bytes per
@@ -43,17 +41,4 @@ def switch_nt(itemsize):
 
 def load():
     """libtemx.so with the temxc_* entry points bound (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    lib = _lib.load()
-    for name, res, args in SIGNATURES:
-        fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.temxc_version())
-    if have != CLIM_VERSION:
-        raise RuntimeError("pytemdiags_amd: %s reports temx_clim version %d, these bindings expect %d; rebuild it "
-                           "(make -C pytemdiags_amd/csrc)" % (_lib.LIB_PATH, have, CLIM_VERSION))
-    _bound = lib
-    return lib
+    return _lib.bind(SIGNATURES, "temxc_version", CLIM_VERSION, "temx_clim")

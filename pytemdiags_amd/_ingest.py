@@ -23,22 +23,7 @@ SIGNATURES = [
                                        _i64, _i, _dp, _dp, _dp, _d, _vp, _i, _i, _i, _vp]),
 ]
 
-_bound = None
-
 
 def load():
     """libtemx.so with the temxi_* entry points bound (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    lib = _lib.load()
-    for name, res, args in SIGNATURES:
-        fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.temxi_version())
-    if have != INGEST_VERSION:
-        raise RuntimeError("pytemdiags_amd: %s reports temx_ingest version %d, these bindings expect %d; rebuild it "
-                           "(make -C pytemdiags_amd/csrc)" % (_lib.LIB_PATH, have, INGEST_VERSION))
-    _bound = lib
-    return lib
+    return _lib.bind(SIGNATURES, "temxi_version", INGEST_VERSION, "temx_ingest")

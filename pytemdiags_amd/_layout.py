@@ -21,22 +21,7 @@ SIGNATURES = [
                              _i, _vp]),
 ]
 
-_bound = None
-
 
 def load():
     """libtemx.so with the temxl_* entry points bound (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    lib = _lib.load()
-    for name, res, args in SIGNATURES:
-        fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.temxl_version())
-    if have != LAYOUT_VERSION:
-        raise RuntimeError("pytemdiags_amd: %s reports temx_layout version %d, these bindings expect %d; rebuild it "
-                           "(make -C pytemdiags_amd/csrc)" % (_lib.LIB_PATH, have, LAYOUT_VERSION))
-    _bound = lib
-    return lib
+    return _lib.bind(SIGNATURES, "temxl_version", LAYOUT_VERSION, "temx_layout")

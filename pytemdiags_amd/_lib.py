@@ -157,6 +157,27 @@ def load():
     return lib
 
 
+_bound = {}
+
+
+def bind(signatures, version_symbol, expected, header):
+    """libtemx.so with the entry points of one more header bound (once per header): ``signatures`` is its table of
+    (name, restype, argtypes), ``version_symbol`` its version function, ``expected`` the version these bindings were
+    written for, ``header`` its name without the extension."""
+    if version_symbol not in _bound:
+        lib = load()
+        for name, res, args in signatures:
+            fn = getattr(lib, name)          # AttributeError here = header/library mismatch
+            fn.restype = res
+            fn.argtypes = args
+        have = int(getattr(lib, version_symbol)())
+        if have != expected:
+            raise RuntimeError("pytemdiags_amd: %s reports %s version %d, these bindings expect %d; rebuild it "
+                               "(make -C pytemdiags_amd/csrc)" % (LIB_PATH, header, have, expected))
+        _bound[version_symbol] = lib
+    return _bound[version_symbol]
+
+
 def check(rc):
     if rc != 0:
         raise TemxError(rc, load().temx_last_error().decode("utf-8", "replace"))

@@ -25,22 +25,7 @@ SIGNATURES = [
                           C.c_double, _vp, _i, _i, _i, _vp]),
 ]
 
-_bound = None
-
 
 def load():
     """libtemx.so with the temxv_* entry points bound (once)."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    lib = _lib.load()
-    for name, res, args in SIGNATURES:
-        fn = getattr(lib, name)          # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    have = int(lib.temxv_version())
-    if have != VERT_VERSION:
-        raise RuntimeError("pytemdiags_amd: %s reports temx_vert version %d, these bindings expect %d; rebuild it "
-                           "(make -C pytemdiags_amd/csrc)" % (_lib.LIB_PATH, have, VERT_VERSION))
-    _bound = lib
-    return lib
+    return _lib.bind(SIGNATURES, "temxv_version", VERT_VERSION, "temx_vert")

@@ -39,6 +39,7 @@
 #include "bin_tables.hpp"
 #include "class_tables.hpp"
 #include "clim_shapes.hpp"
+#include "field_args.hpp"
 #include "host_math.hpp"
 #include "launch_shapes.hpp"
 
@@ -71,6 +72,10 @@ static int fail(int code, const char* fmt, ...) {
                   #expr, hipGetErrorString(e_));                                         \
     }                                                                                    \
   } while (0)
+
+// the argument rules of field_args.hpp: a refused call returns through fail()
+#define ARGCHK(expr) \
+  do { if (const Refusal r_ = (expr)) return fail(r_.code, "%s", r_.msg); } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // plan
@@ -3844,74 +3849,39 @@ int temx_selftest_exception(int kind) try {
 // ---- vertical interpolation (include/temx_vert.h) ------------------------------------------------
 int temxv_version(void) { return 100; }
 
+// the level tables of a remap on `device`, through the cache of vert_tables; hyam null: no hybrid coefficients
+static int vert_tab_on(int device, int nlev, const double* hyam, const double* hybm, int nplev, const double* plev,
+                       int method, VertTab* tb) {
+  const double* dev = nullptr;
+  if (int rc = vert_tables(device, vert_table_host(nlev, hyam, hybm, nplev, plev, method), &dev)) return rc;
+  *tb = VertTab{};
+  if (hyam) tb->hyam = dev, tb->hybm = dev + nlev, dev += 2 * (size_t)nlev;
+  tb->pt = dev, tb->xt = dev + nplev;
+  return TEMX_OK;
+}
+
 int temxv_interp(int device, int nf, const void* const* src_host, void* const* dst_host, int dtype, int64_t ncol,
                  int nlev, int64_t nt, int nplev, const double* plev_pa_host, int pmode, const double* hyam_host,
                  const double* hybm_host, double p0_hybrid, const void* ps_or_p, int p_dtype, int method, int edge,
                  void* stream) try {
-  if (nf < 1 || nf > TEMXV_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", (int)TEMXV_NF_MAX, nf);
-  if (!src_host || !dst_host || !plev_pa_host || !ps_or_p) return fail(TEMX_EINVAL, "null argument");
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
-  if (p_dtype != TEMX_F64 && p_dtype != TEMX_F32) return fail(TEMX_EINVAL, "p_dtype must be TEMX_F64 or TEMX_F32");
+  ARGCHK(check_nf(nf, TEMXV_NF_MAX) | check_null(src_host, "src_host") | check_null(dst_host, "dst_host") |
+         check_null(plev_pa_host, "plev_pa_host") | check_null(ps_or_p, "ps_or_p") | check_dtype(dtype, "dtype") |
+         check_dtype(p_dtype, "p_dtype") | check_method_edge(method, edge) | check_sizes(ncol, nlev, nt, "nt", /*remap=*/true, nplev));
   if (pmode != TEMXV_P_HYBRID && pmode != TEMXV_P_FIELD) return fail(TEMX_EINVAL, "pmode must be TEMXV_P_HYBRID or TEMXV_P_FIELD");
-  if (method != TEMXV_LOG && method != TEMXV_LINEAR) return fail(TEMX_EINVAL, "method must be TEMXV_LOG or TEMXV_LINEAR");
-  if (edge != TEMXV_EDGE_NAN && edge != TEMXV_EDGE_HOLD) return fail(TEMX_EINVAL, "edge must be TEMXV_EDGE_NAN or TEMXV_EDGE_HOLD");
-  if (ncol < 1 || nt < 1 || nplev < 1 || nlev < 2) return fail(TEMX_EINVAL, "sizes must be positive (nlev at least 2)");
-  if (nlev > (1 << 20) || nplev > (1 << 20) || nt > (int64_t(1) << 31) || ncol > (int64_t(1) << 40))
-    return fail(TEMX_EINVAL, "sizes out of range");
   const bool hyb = pmode == TEMXV_P_HYBRID;
   if (hyb && (!hyam_host || !hybm_host)) return fail(TEMX_EINVAL, "hybrid mode needs hyam and hybm");
-  if (hyb && !std::isfinite(p0_hybrid)) return fail(TEMX_EINVAL, "p0_hybrid is not finite");
-  for (int j = 0; j < nplev; ++j)
-    if (!(plev_pa_host[j] > 0.0) || !std::isfinite(plev_pa_host[j]) || (j && !(plev_pa_host[j] > plev_pa_host[j - 1])))
-      return fail(TEMX_EINVAL, "plev must be positive, finite and strictly ascending (entry %d)", j);
-  if (hyb)
-    for (int k = 0; k < nlev; ++k)
-      if (!std::isfinite(hyam_host[k]) || !std::isfinite(hybm_host[k]))
-        return fail(TEMX_EINVAL, "hyam / hybm entry %d is not finite", k);
-  const size_t tsz = dtype == TEMX_F64 ? 8 : 4, psz = p_dtype == TEMX_F64 ? 8 : 4;
-  const size_t in_bytes = (size_t)ncol * nlev * nt * tsz, out_bytes = (size_t)ncol * nplev * nt * tsz;
-  const size_t p_bytes = hyb ? (size_t)ncol * nt * psz : (size_t)ncol * nlev * nt * psz;
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-  };
-  if ((uintptr_t)ps_or_p % psz) return fail(TEMX_EINVAL, "ps_or_p is not aligned to its element size");
-  for (int f = 0; f < nf; ++f) {
-    if (!src_host[f] || !dst_host[f]) return fail(TEMX_EINVAL, "null field pointer (field %d)", f);
-    if ((uintptr_t)src_host[f] % tsz || (uintptr_t)dst_host[f] % tsz)
-      return fail(TEMX_EINVAL, "field %d is not aligned to its element size", f);
-    if (overlap(dst_host[f], out_bytes, ps_or_p, p_bytes)) return fail(TEMX_EINVAL, "dst %d overlaps the pressure input", f);
-    for (int g = 0; g < nf; ++g) {
-      if (src_host[g] && overlap(dst_host[f], out_bytes, src_host[g], in_bytes))
-        return fail(TEMX_EINVAL, "dst %d overlaps src %d", f, g);
-      if (g < f && overlap(dst_host[f], out_bytes, dst_host[g], out_bytes))
-        return fail(TEMX_EINVAL, "dst %d overlaps dst %d", f, g);
-    }
-  }
+  if (!hyb) hyam_host = hybm_host = nullptr;   // read in hybrid mode only
+  ARGCHK(check_levels(nplev, plev_pa_host, nlev, hyam_host, hybm_host, p0_hybrid));
+  int src_dtype[TEMXV_NF_MAX];
+  std::fill(src_dtype, src_dtype + nf, dtype);
+  const size_t in_elems = (size_t)ncol * nlev * nt;
+  ARGCHK(check_fields({nf, src_host, src_dtype, in_elems, dst_host, "dst", dtype, (size_t)ncol * nplev * nt, ps_or_p,
+                       "ps_or_p", p_dtype, hyb ? (size_t)ncol * nt : in_elems}));
   int map = 0;   // 0 by row length, 1 lanes along time, 2 slab staged
   if (const char* m = getenv("TEMXV_MAP")) map = !strcmp(m, "time") ? 1 : !strcmp(m, "slab") ? 2 : 0;
-
-  // tables: [hyam | hybm] (hybrid) pt xt
-  std::vector<double> host;
-  host.reserve((hyb ? 2 * (size_t)nlev : 0) + 2 * (size_t)nplev + 1);
-  if (hyb) {
-    host.insert(host.end(), hyam_host, hyam_host + nlev);
-    host.insert(host.end(), hybm_host, hybm_host + nlev);
-  }
-  host.insert(host.end(), plev_pa_host, plev_pa_host + nplev);
-  for (int j = 0; j < nplev; ++j) host.push_back(method == TEMXV_LOG ? std::log(plev_pa_host[j]) : plev_pa_host[j]);
-  host.push_back((double)method);
   HIPCHK(hipSetDevice(device));
-  const double* dev = nullptr;
-  if (int rc = vert_tables(device, host, &dev)) return rc;
-  VertTab tb{};
-  if (hyb) {
-    tb.hyam = dev;
-    tb.hybm = dev + nlev;
-    dev += 2 * (size_t)nlev;
-  }
-  tb.pt = dev;
-  tb.xt = dev + nplev;
+  VertTab tb;
+  if (int rc = vert_tab_on(device, nlev, hyam_host, hybm_host, nplev, plev_pa_host, method, &tb)) return rc;
   const int p_f32 = p_dtype == TEMX_F32, logp = method == TEMXV_LOG, hold = edge == TEMXV_EDGE_HOLD;
   hipStream_t st = S_(stream);
 #define TEMXV_GO(T, H) \
@@ -3927,49 +3897,13 @@ int temxl_version(void) { return 100; }
 int temxl_to_engine(int device, int nf, const void* const* src_host, const int* src_dtype_host, void* const* dst_host,
                     int dst_dtype, int64_t ncol, int nlev, int64_t nt_src, int64_t t0, int64_t ntb, int flags,
                     void* stream) try {
-  if (nf < 1 || nf > TEMXL_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", (int)TEMXL_NF_MAX, nf);
-  if (!src_host) return fail(TEMX_EINVAL, "src_host is null");
-  if (!src_dtype_host) return fail(TEMX_EINVAL, "src_dtype_host is null");
-  if (!dst_host) return fail(TEMX_EINVAL, "dst_host is null");
-  if (dst_dtype != TEMX_F64 && dst_dtype != TEMX_F32) return fail(TEMX_EINVAL, "dst_dtype must be TEMX_F64 or TEMX_F32");
-  if (ncol < 1) return fail(TEMX_EINVAL, "ncol must be at least 1");
-  if (nlev < 1) return fail(TEMX_EINVAL, "nlev must be at least 1");
-  if (nt_src < 1) return fail(TEMX_EINVAL, "nt_src must be at least 1");
-  if (ntb < 1) return fail(TEMX_EINVAL, "ntb must be at least 1");
-  if (t0 < 0) return fail(TEMX_EINVAL, "t0 must not be negative");
-  if (nlev > (1 << 20) || nt_src > (int64_t(1) << 31) || ncol > (int64_t(1) << 40))
-    return fail(TEMX_EINVAL, "sizes out of range (ncol, nlev or nt_src)");
-  if (ntb > nt_src || t0 > nt_src - ntb)
-    return fail(TEMX_EINVAL, "t0 + ntb = %lld exceeds nt_src = %lld", (long long)(t0 + ntb), (long long)nt_src);
-  if (flags & ~(int)TEMXL_FLIP_LEV) return fail(TEMX_EINVAL, "flags has unknown bits (0x%x)", (unsigned)flags);
-  const double total = (double)ncol * (double)nlev * (double)nt_src;
-  if (total > 281474976710656.0) return fail(TEMX_EINVAL, "sizes out of range (ncol * nlev * nt_src above 2^48)");
-  const size_t dsz = dst_dtype == TEMX_F64 ? 8 : 4;
-  const size_t src_elems = (size_t)ncol * nlev * nt_src, dst_bytes = (size_t)ncol * nlev * ntb * dsz;
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-  };
-  unsigned src_f32 = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (src_dtype_host[f] != TEMX_F64 && src_dtype_host[f] != TEMX_F32)
-      return fail(TEMX_EINVAL, "src_dtype %d must be TEMX_F64 or TEMX_F32", f);
-    if (src_dtype_host[f] == TEMX_F64 && dst_dtype == TEMX_F32)
-      return fail(TEMX_EINVAL, "src_dtype %d is TEMX_F64 but dst_dtype is TEMX_F32: this call does not narrow", f);
-    if (src_dtype_host[f] == TEMX_F32) src_f32 |= 1u << f;
-    if (!src_host[f]) return fail(TEMX_EINVAL, "src %d is null", f);
-    if (!dst_host[f]) return fail(TEMX_EINVAL, "dst %d is null", f);
-    if ((uintptr_t)src_host[f] % (src_dtype_host[f] == TEMX_F64 ? 8 : 4))
-      return fail(TEMX_EINVAL, "src %d is not aligned to its element size", f);
-    if ((uintptr_t)dst_host[f] % dsz) return fail(TEMX_EINVAL, "dst %d is not aligned to its element size", f);
-  }
-  for (int f = 0; f < nf; ++f)
-    for (int g = 0; g < nf; ++g) {
-      if (overlap(dst_host[f], dst_bytes, src_host[g], src_elems * (src_dtype_host[g] == TEMX_F64 ? 8 : 4)))
-        return fail(TEMX_EINVAL, "dst %d overlaps src %d", f, g);
-      if (g < f && overlap(dst_host[f], dst_bytes, dst_host[g], dst_bytes))
-        return fail(TEMX_EINVAL, "dst %d overlaps dst %d", f, g);
-    }
+  ARGCHK(check_nf(nf, TEMXL_NF_MAX) | check_null(src_host, "src_host") | check_null(src_dtype_host, "src_dtype_host") |
+         check_null(dst_host, "dst_host") | check_dtype(dst_dtype, "dst_dtype") | check_sizes(ncol, nlev, nt_src, "nt_src") |
+         check_window(nt_src, t0, ntb) | check_flags(flags, TEMXL_FLIP_LEV));
+  ARGCHK(check_fields({nf, src_host, src_dtype_host, (size_t)ncol * nlev * nt_src, dst_host, "dst", dst_dtype,
+                       (size_t)ncol * nlev * ntb}));
+  const size_t dsz = dtype_size(dst_dtype);
+  const unsigned src_f32 = f32_mask(nf, src_dtype_host);
   if (ncol > (int64_t(1) << 35)) return fail(TEMX_EUNSUPPORTED, "too many columns for one launch");
   const LayoutTile tl = layout_tile(ncol, nlev, ntb, dsz);
   const int64_t grid = (int64_t)tl.nct * nf * tl.nlt * tl.ntt;
@@ -4001,63 +3935,18 @@ int temxi_records_to_pressure(int device, int nf, const void* const* src_host, c
                               int64_t ntb, int nplev, const double* plev_pa_host, const double* hyam_host,
                               const double* hybm_host, double p0_hybrid, const void* ps, int ps_dtype, int method,
                               int edge, void* stream) try {
-  if (nf < 1 || nf > TEMXI_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", (int)TEMXI_NF_MAX, nf);
-  if (!src_host) return fail(TEMX_EINVAL, "src_host is null");
-  if (!src_dtype_host) return fail(TEMX_EINVAL, "src_dtype_host is null");
-  if (!dst_host) return fail(TEMX_EINVAL, "dst_host is null");
+  ARGCHK(check_nf(nf, TEMXI_NF_MAX) | check_null(src_host, "src_host") | check_null(src_dtype_host, "src_dtype_host") |
+         check_null(dst_host, "dst_host"));
   if (!plev_pa_host || !hyam_host || !hybm_host) return fail(TEMX_EINVAL, "plev_pa_host, hyam_host or hybm_host is null");
-  if (!ps) return fail(TEMX_EINVAL, "ps is null");
-  if (dst_dtype != TEMX_F64 && dst_dtype != TEMX_F32) return fail(TEMX_EINVAL, "dst_dtype must be TEMX_F64 or TEMX_F32");
-  if (ps_dtype != TEMX_F64 && ps_dtype != TEMX_F32) return fail(TEMX_EINVAL, "ps_dtype must be TEMX_F64 or TEMX_F32");
-  if (method != TEMXV_LOG && method != TEMXV_LINEAR) return fail(TEMX_EINVAL, "method must be TEMXV_LOG or TEMXV_LINEAR");
-  if (edge != TEMXV_EDGE_NAN && edge != TEMXV_EDGE_HOLD) return fail(TEMX_EINVAL, "edge must be TEMXV_EDGE_NAN or TEMXV_EDGE_HOLD");
-  if (ncol < 1 || nt_src < 1 || ntb < 1 || nplev < 1 || nlev < 2)
-    return fail(TEMX_EINVAL, "sizes must be positive (nlev at least 2)");
-  if (t0 < 0) return fail(TEMX_EINVAL, "t0 must not be negative");
-  if (nlev > (1 << 20) || nplev > (1 << 20) || nt_src > (int64_t(1) << 31) || ncol > (int64_t(1) << 40))
-    return fail(TEMX_EINVAL, "sizes out of range (ncol, nlev, nplev or nt_src)");
-  if (ntb > nt_src || t0 > nt_src - ntb)
-    return fail(TEMX_EINVAL, "t0 + ntb = %lld exceeds nt_src = %lld", (long long)(t0 + ntb), (long long)nt_src);
-  if ((double)ncol * (double)std::max(nlev, nplev) * (double)nt_src > 281474976710656.0)
-    return fail(TEMX_EINVAL, "sizes out of range (ncol * levels * nt_src above 2^48)");
-  if (!std::isfinite(p0_hybrid)) return fail(TEMX_EINVAL, "p0_hybrid is not finite");
-  for (int j = 0; j < nplev; ++j)
-    if (!(plev_pa_host[j] > 0.0) || !std::isfinite(plev_pa_host[j]) || (j && !(plev_pa_host[j] > plev_pa_host[j - 1])))
-      return fail(TEMX_EINVAL, "plev must be positive, finite and strictly ascending (entry %d)", j);
-  for (int k = 0; k < nlev; ++k)
-    if (!std::isfinite(hyam_host[k]) || !std::isfinite(hybm_host[k]))
-      return fail(TEMX_EINVAL, "hyam / hybm entry %d is not finite", k);
-  const size_t dsz = dst_dtype == TEMX_F64 ? 8 : 4, psz = ps_dtype == TEMX_F64 ? 8 : 4;
-  const size_t src_elems = (size_t)ncol * nlev * nt_src, dst_bytes = (size_t)ncol * nplev * ntb * dsz;
-  const size_t ps_bytes = (size_t)ncol * nt_src * psz;
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-  };
-  if ((uintptr_t)ps % psz) return fail(TEMX_EINVAL, "ps is not aligned to its element size");
-  unsigned src_f32 = 0;
-  size_t ssz = 8;
-  for (int f = 0; f < nf; ++f) {
-    if (src_dtype_host[f] != TEMX_F64 && src_dtype_host[f] != TEMX_F32)
-      return fail(TEMX_EINVAL, "src_dtype %d must be TEMX_F64 or TEMX_F32", f);
-    if (src_dtype_host[f] == TEMX_F64 && dst_dtype == TEMX_F32)
-      return fail(TEMX_EINVAL, "src_dtype %d is TEMX_F64 but dst_dtype is TEMX_F32: this call does not narrow", f);
-    if (src_dtype_host[f] == TEMX_F32) src_f32 |= 1u << f, ssz = 4;
-    if (!src_host[f]) return fail(TEMX_EINVAL, "src %d is null", f);
-    if (!dst_host[f]) return fail(TEMX_EINVAL, "dst %d is null", f);
-    if ((uintptr_t)src_host[f] % (src_dtype_host[f] == TEMX_F64 ? 8 : 4))
-      return fail(TEMX_EINVAL, "src %d is not aligned to its element size", f);
-    if ((uintptr_t)dst_host[f] % dsz) return fail(TEMX_EINVAL, "dst %d is not aligned to its element size", f);
-  }
-  for (int f = 0; f < nf; ++f) {
-    if (overlap(dst_host[f], dst_bytes, ps, ps_bytes)) return fail(TEMX_EINVAL, "dst %d overlaps ps", f);
-    for (int g = 0; g < nf; ++g) {
-      if (overlap(dst_host[f], dst_bytes, src_host[g], src_elems * (src_dtype_host[g] == TEMX_F64 ? 8 : 4)))
-        return fail(TEMX_EINVAL, "dst %d overlaps src %d", f, g);
-      if (g < f && overlap(dst_host[f], dst_bytes, dst_host[g], dst_bytes))
-        return fail(TEMX_EINVAL, "dst %d overlaps dst %d", f, g);
-    }
-  }
+  ARGCHK(check_null(ps, "ps") | check_dtype(dst_dtype, "dst_dtype") | check_dtype(ps_dtype, "ps_dtype") |
+         check_method_edge(method, edge) | check_sizes(ncol, nlev, nt_src, "nt_src", /*remap=*/true, nplev) |
+         check_window(nt_src, t0, ntb, /*remap=*/true));
+  ARGCHK(check_levels(nplev, plev_pa_host, nlev, hyam_host, hybm_host, p0_hybrid));
+  ARGCHK(check_fields({nf, src_host, src_dtype_host, (size_t)ncol * nlev * nt_src, dst_host, "dst", dst_dtype,
+                       (size_t)ncol * nplev * ntb, ps, "ps", ps_dtype, (size_t)ncol * nt_src}));
+  const size_t dsz = dtype_size(dst_dtype);
+  const unsigned src_f32 = f32_mask(nf, src_dtype_host);
+  const size_t ssz = src_f32 ? 4 : 8;   // the narrowest source
   if (ncol > (int64_t(1) << 34)) return fail(TEMX_EUNSUPPORTED, "too many columns for one launch");
   IngestTile tl{};
   size_t lds = 0;
@@ -4067,23 +3956,9 @@ int temxi_records_to_pressure(int device, int nf, const void* const* src_host, c
   if (grid >= (int64_t(1) << 32) / INGEST_THREADS)   // HIP takes fewer than 2^32 threads per grid dimension
     return fail(TEMX_EUNSUPPORTED, "too many tiles for one launch (%lld): move the window in parts", (long long)grid);
   if (lds > (size_t)INGEST_LDS_BYTES) return fail(TEMX_EINTERNAL, "ingest tile of %zu bytes exceeds its LDS budget", lds);
-
-  // tables: hyam hybm pt xt, the set temxv_interp forms in hybrid mode, through the same cache
-  std::vector<double> host;
-  host.reserve(2 * (size_t)nlev + 2 * (size_t)nplev + 1);
-  host.insert(host.end(), hyam_host, hyam_host + nlev);
-  host.insert(host.end(), hybm_host, hybm_host + nlev);
-  host.insert(host.end(), plev_pa_host, plev_pa_host + nplev);
-  for (int j = 0; j < nplev; ++j) host.push_back(method == TEMXV_LOG ? std::log(plev_pa_host[j]) : plev_pa_host[j]);
-  host.push_back((double)method);
   HIPCHK(hipSetDevice(device));
-  const double* dev = nullptr;
-  if (int rc = vert_tables(device, host, &dev)) return rc;
-  VertTab tb{};
-  tb.hyam = dev;
-  tb.hybm = dev + nlev;
-  tb.pt = dev + 2 * (size_t)nlev;
-  tb.xt = tb.pt + nplev;
+  VertTab tb;   // the tables temxv_interp forms in hybrid mode, through the same cache
+  if (int rc = vert_tab_on(device, nlev, hyam_host, hybm_host, nplev, plev_pa_host, method, &tb)) return rc;
   IngestPtrs fp{};
   for (int f = 0; f < nf; ++f) fp.src[f] = src_host[f], fp.dst[f] = dst_host[f];
   const int ps_f32 = ps_dtype == TEMX_F32, logp = method == TEMXV_LOG, hold = edge == TEMXV_EDGE_HOLD;
@@ -4108,40 +3983,10 @@ int temxc_version(void) { return 100; }
 
 int temxc_time_sum(int device, int nf, const void* const* src_host, const int* src_dtype_host, double* const* acc_host,
                    int64_t ncol, int nlev, int64_t nt, int flags, void* stream) try {
-  if (nf < 1 || nf > TEMXC_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", (int)TEMXC_NF_MAX, nf);
-  if (!src_host) return fail(TEMX_EINVAL, "src_host is null");
-  if (!src_dtype_host) return fail(TEMX_EINVAL, "src_dtype_host is null");
-  if (!acc_host) return fail(TEMX_EINVAL, "acc_host is null");
-  if (ncol < 1) return fail(TEMX_EINVAL, "ncol must be at least 1");
-  if (nlev < 1) return fail(TEMX_EINVAL, "nlev must be at least 1");
-  if (nt < 1) return fail(TEMX_EINVAL, "nt must be at least 1");
-  if (nlev > (1 << 20) || nt > (int64_t(1) << 31) || ncol > (int64_t(1) << 40))
-    return fail(TEMX_EINVAL, "sizes out of range (ncol, nlev or nt)");
-  if ((double)ncol * (double)nlev * (double)nt > 281474976710656.0)
-    return fail(TEMX_EINVAL, "sizes out of range (ncol * nlev * nt above 2^48)");
-  if (flags & ~(int)TEMXC_ACCUMULATE) return fail(TEMX_EINVAL, "flags has unknown bits (0x%x)", (unsigned)flags);
+  ARGCHK(check_nf(nf, TEMXC_NF_MAX) | check_null(src_host, "src_host") | check_null(src_dtype_host, "src_dtype_host") |
+         check_null(acc_host, "acc_host") | check_sizes(ncol, nlev, nt, "nt") | check_flags(flags, TEMXC_ACCUMULATE));
   const int64_t rows = ncol * nlev;
-  const size_t src_elems = (size_t)rows * nt, acc_bytes = (size_t)rows * sizeof(double);
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-  };
-  for (int f = 0; f < nf; ++f) {
-    if (src_dtype_host[f] != TEMX_F64 && src_dtype_host[f] != TEMX_F32)
-      return fail(TEMX_EINVAL, "src_dtype %d must be TEMX_F64 or TEMX_F32", f);
-    if (!src_host[f]) return fail(TEMX_EINVAL, "src %d is null", f);
-    if (!acc_host[f]) return fail(TEMX_EINVAL, "acc %d is null", f);
-    if ((uintptr_t)src_host[f] % (src_dtype_host[f] == TEMX_F64 ? 8 : 4))
-      return fail(TEMX_EINVAL, "src %d is not aligned to its element size", f);
-    if ((uintptr_t)acc_host[f] % sizeof(double)) return fail(TEMX_EINVAL, "acc %d is not aligned to its element size", f);
-  }
-  for (int f = 0; f < nf; ++f)
-    for (int g = 0; g < nf; ++g) {
-      if (overlap(acc_host[f], acc_bytes, src_host[g], src_elems * (src_dtype_host[g] == TEMX_F64 ? 8 : 4)))
-        return fail(TEMX_EINVAL, "acc %d overlaps src %d", f, g);
-      if (g < f && overlap(acc_host[f], acc_bytes, acc_host[g], acc_bytes))
-        return fail(TEMX_EINVAL, "acc %d overlaps acc %d", f, g);
-    }
+  ARGCHK(check_fields({nf, src_host, src_dtype_host, (size_t)rows * nt, (void* const*)acc_host, "acc", TEMX_F64, (size_t)rows}));
   // the fp64 and the fp32 sources go in a launch each: their rows are cut differently (clim_shapes.hpp)
   ClimPtrs p64{}, p32{};
   int n64 = 0, n32 = 0;
