@@ -39,6 +39,7 @@
 #include "bin_tables.hpp"
 #include "class_tables.hpp"
 #include "clim_shapes.hpp"
+#include "dispatch.hpp"
 #include "field_args.hpp"
 #include "host_math.hpp"
 #include "launch_shapes.hpp"
@@ -310,6 +311,37 @@ static int lds_attr_once(std::atomic<uint64_t>& done, int device, const void* fn
   return TEMX_OK;
 }
 
+// One launch: raise the dynamic-LDS limit of kernel Kern on this device if nobody has yet (to attr_bytes when given,
+// else to what this launch asks for), launch, read the launch error.  The flag is the kernel instantiation's own.
+template <auto Kern>
+static std::atomic<uint64_t> lds_attr_done{0};   // one bit per device
+
+template <auto Kern, typename... A>
+__attribute__((noinline))   // keeps each dispatch branch a call, not an inlined launch body
+static int launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(Kern, grid, block, lds_bytes, st, args...);
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+template <auto Kern, int attr_bytes = 0, typename... A>
+static int launch_lds(int device, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, A... args) {
+  const int limit = attr_bytes ? attr_bytes : (int)lds_bytes;
+  if (int rc = lds_attr_once(lds_attr_done<Kern>, device, reinterpret_cast<const void*>(Kern), limit)) return rc;
+  return launch<Kern>(grid, block, lds_bytes, st, args...);
+}
+
+// the one dtype refusal; by_dtype: f(TypeTag<double or float>) (dispatch.hpp), or that refusal
+static int bad_dtype() { return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32"); }
+template <typename F>
+static int by_dtype(int dtype, F&& f) {
+  int rc = TEMX_OK;
+  return dispatch_dtype(dtype, rc, f) ? rc : bad_dtype();
+}
+
+// the basis kernels keep one row of K values per thread: 64 in registers, 512 (L <= 511) in scratch
+template <typename F>
+static int by_basis_rows(int K, F&& f) { return K <= 64 ? f(Int<64>{}) : f(Int<512>{}); }
+
 template <typename T>
 static int upload(DevBuf& b, const std::vector<T>& v) { return upload(b, v.data(), v.size() * sizeof(T)); }
 static int os_upload_blocks(temx_plan* pl);
@@ -372,54 +404,28 @@ static int proj_wps(int NF, int dpw) {
   return dpw == 1 ? ProjCfgE::WPS : ProjCfgC::WPS;
 }
 
-template <typename T, int NF, typename Cfg>
-static int launch_project_c(temx_plan* pl, const FieldPtrs<NF>& fp, int64_t D, const double* colscale,
-                            int sfield, double* partial, const Split& sp, hipStream_t st, int tb_off,
-                            int Kloc) {
-  dim3 grid(sp.grid), block(256);
-#define TEMX_LP(TBv)                                                                                  \
-  hipLaunchKernelGGL((project_kernel<T, NF, Cfg::NFW, TBv, Cfg::PD, Cfg::WPS>), grid, block, 0, st, fp, \
-                     pl->N, D, Kloc, pl->yproj_ptr(), pl->stride, tb_off, pl->nchunk, colscale,       \
-                     sfield, partial, sp.nsplit, sp.ndt)
-  switch (pl->TB) {
-    case 4: TEMX_LP(4); break;
-    case 8: TEMX_LP(8); break;
-    case 13: TEMX_LP(13); break;
-    default: TEMX_LP(16); break;
-  }
-#undef TEMX_LP
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
-}
-
 constexpr int SYM_PROJ_E_WPS = 3;
 struct ProjCfg3 { static constexpr int NFW = 3, PD = 1, WPS = 2; };   // the 3 eddy products (large-L path)
-
-template <typename T, int NF>
-static int launch_project_t(temx_plan* pl, const FieldPtrs<NF>& fp, int64_t D, const double* colscale,
-                            int sfield, double* partial, const Split& sp, hipStream_t st, int tb_off,
-                            int Kloc) {
-  if constexpr (NF == 1) {
-    return launch_project_c<T, NF, ProjCfg1>(pl, fp, D, colscale, sfield, partial, sp, st, tb_off, Kloc);
-  } else if constexpr (NF == 3) {
-    return launch_project_c<T, NF, ProjCfg3>(pl, fp, D, colscale, sfield, partial, sp, st, tb_off, Kloc);
-  } else {
-    if (sp.dpw == 1)
-      return launch_project_c<T, NF, ProjCfgE>(pl, fp, D, colscale, sfield, partial, sp, st, tb_off, Kloc);
-    return launch_project_c<T, NF, ProjCfgC>(pl, fp, D, colscale, sfield, partial, sp, st, tb_off, Kloc);
-  }
-}
 
 template <int NF>
 static int launch_project(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int64_t D,
                           const double* colscale, int sfield, double* partial, const Split& sp,
                           hipStream_t st, int tb_off = 0, int Kloc = -1) {
   if (Kloc < 0) Kloc = pl->K;
-  if (dtype == TEMX_F64)
-    return launch_project_t<double, NF>(pl, fp, D, colscale, sfield, partial, sp, st, tb_off, Kloc);
-  if (dtype == TEMX_F32)
-    return launch_project_t<float, NF>(pl, fp, D, colscale, sfield, partial, sp, st, tb_off, Kloc);
-  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  return by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto go = [&](auto cfg) {
+      using Cfg = decltype(cfg);
+      return dispatch(TBValues{}, pl->TB, [&](auto tb) {
+        return launch<project_kernel<T, NF, Cfg::NFW, decltype(tb)::value, Cfg::PD, Cfg::WPS>>(
+            dim3(sp.grid), dim3(256), 0, st, fp, pl->N, D, Kloc, pl->yproj_ptr(), pl->stride, tb_off, pl->nchunk, colscale,
+            sfield, partial, sp.nsplit, sp.ndt);
+      });
+    };
+    if constexpr (NF == 1) return go(ProjCfg1{});
+    else if constexpr (NF == 3) return go(ProjCfg3{});
+    else return sp.dpw == 1 ? go(ProjCfgE{}) : go(ProjCfgC{});
+  });
 }
 
 // B[n] = (addend ? addend : 0) + sum over the nsplit slabs; slab sp starts at partial + sp * stride
@@ -474,74 +480,35 @@ static int launch_solve(temx_plan* pl, const double* B, int NF, int64_t D, doubl
     int mbs = SOLVE_MB;
     while (mbs > 4 && (int64_t)gx * NF * ((nmb + mbs - 1) / mbs) < pl->num_cu / 2) mbs -= 4;
     dim3 grid((unsigned)gx, NF, Xb ? (nmb + mbs - 1) / mbs : 1);
-#define TEMX_LS(TBv)                                                                                  \
-  do {                                                                                                \
-    const size_t slds = ((size_t)TBv * TBv + (size_t)SOLVE_MB * TBv) * 16 * sizeof(double);           \
-    static std::atomic<uint64_t> attr{0};                                                             \
-    if (int rc_ = lds_attr_once(attr, pl->device, reinterpret_cast<const void*>(solve_mfma_kernel<TBv>), (int)slds)) \
-      return rc_;                                                                                     \
-    hipLaunchKernelGGL(solve_mfma_kernel<TBv>, grid, dim3(256), slds, st, B, pl->K, pl->M, D,         \
-                       pl->gblk.d(), pl->ypblk.d(), C, Xb, mbs);                                      \
-  } while (0)
-    switch (pl->TB) {
-      case 4: TEMX_LS(4); break;
-      case 8: TEMX_LS(8); break;
-      case 13: TEMX_LS(13); break;
-      default: TEMX_LS(16); break;
-    }
-#undef TEMX_LS
-    HIPCHK(hipGetLastError());
-    return TEMX_OK;
+    return dispatch(TBValues{}, pl->TB, [&](auto tb) {
+      constexpr int TBv = decltype(tb)::value;
+      const size_t slds = ((size_t)TBv * TBv + (size_t)SOLVE_MB * TBv) * 16 * sizeof(double);
+      return launch_lds<solve_mfma_kernel<TBv>>(pl->device, grid, dim3(256), slds, st, B, pl->K, pl->M, D, pl->gblk.d(),
+                                                pl->ypblk.d(), C, Xb, mbs);
+    });
   }
   // 16 waves per block (the solve is latency bound: one round of dot products per phase); slices of
   // 64 output latitudes = one zonal-mean output per thread
   const int ms = Xb ? (pl->M + 63) / 64 : 1;
   dim3 grid((unsigned)((D + 15) / 16), NF, ms);
-  {
-    const size_t slds = (size_t)2 * pl->K4 * 17 * sizeof(double);
-    static std::atomic<uint64_t> attr{0};
-    if (int rc = lds_attr_once(attr, pl->device, reinterpret_cast<const void*>(solve_kernel), 160 * 1024)) return rc;
-    hipLaunchKernelGGL(solve_kernel, grid, dim3(1024), slds, st, B, pl->K, pl->K4, pl->M, D, pl->Ginv.d(),
-                       pl->Qp.d(), C, Xb);
-  }
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
-}
-
-template <typename T, int MODE, int DPW, int KIND>
-static int launch_eddy_d(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
-                         const Split& sp, const EddyOut& eo, hipStream_t st) {
-  dim3 grid(sp.grid), block(512);
-  constexpr int NFR = KIND == 1 ? 3 : 4;
-#define TEMX_LE(TBv)                                                                                  \
-  do {                                                                                                \
-    auto kern = eddy_kernel<T, TBv, MODE, DPW, KIND>;                                                 \
-    const size_t lds = ((size_t)DPW * NFR * TBv * 64 + 8 * EDDY_GR * TBv * 16) * sizeof(double);      \
-    static std::atomic<uint64_t> attr_set{0};   /* per instantiation, one bit per device */           \
-    if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) \
-      return rc_;                                                                                     \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, fp, pl->N, pl->D, pl->K, pl->yblk.d(),             \
-                       pl->nchunk, pl->colscale.d(), C, partial, sp.nsplit, sp.ndt, eo);              \
-  } while (0)
-  switch (pl->TB) {
-    case 4: TEMX_LE(4); break;
-    case 8: TEMX_LE(8); break;
-    case 13: TEMX_LE(13); break;
-    default: TEMX_LE(16); break;
-  }
-#undef TEMX_LE
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  const size_t slds = (size_t)2 * pl->K4 * 17 * sizeof(double);
+  return launch_lds<solve_kernel, 160 * 1024>(pl->device, grid, dim3(1024), slds, st, B, pl->K, pl->K4, pl->M, D,
+      pl->Ginv.d(), pl->Qp.d(), C, Xb);
 }
 
 template <typename T, int MODE, int KIND>
 static int launch_eddy_t(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
                          const Split& sp, const EddyOut& eo, hipStream_t st) {
-  switch (sp.dpw) {
-    case 1: return launch_eddy_d<T, MODE, 1, KIND>(pl, fp, C, partial, sp, eo, st);
-    case 2: return launch_eddy_d<T, MODE, 2, KIND>(pl, fp, C, partial, sp, eo, st);
-    default: return launch_eddy_d<T, MODE, 4, KIND>(pl, fp, C, partial, sp, eo, st);
-  }
+  constexpr int NFR = KIND == 1 ? 3 : 4;
+  return dispatch(DpwValues{}, sp.dpw, [&](auto dpw) {
+    return dispatch(TBValues{}, pl->TB, [&](auto tb) {
+      constexpr int DPW = decltype(dpw)::value, TBv = decltype(tb)::value;
+      const size_t lds = ((size_t)DPW * NFR * TBv * 64 + 8 * EDDY_GR * TBv * 16) * sizeof(double);
+      return launch_lds<eddy_kernel<T, TBv, MODE, DPW, KIND>>(pl->device, dim3(sp.grid), dim3(512), lds, st, fp, pl->N, pl->D,
+                                                              pl->K, pl->yblk.d(), pl->nchunk, pl->colscale.d(), C, partial,
+                                                              sp.nsplit, sp.ndt, eo);
+    });
+  });
 }
 
 // native-grid reconstruction out[row][d] = sum_l Y0[row0 + row][l] C[l][d] for rows [row0, row0 + nrows),
@@ -553,26 +520,18 @@ static int launch_recon(temx_plan* pl, int64_t D, const double* C, double* out, 
   const double* yb0 = pl->yblk.d() + (row0 / 4) * pl->stride * 16;
   Split sp = choose_split(D, nch, 2 * pl->num_cu);
   dim3 grid(sp.grid), block(256);
-#define TEMX_LR(TBv, tboff, Cs, acc)                                                                  \
-  do {                                                                                                \
-    auto kern = recon_kernel<TBv>;                                                                    \
-    const size_t lds = (size_t)4 * TBv * 64 * sizeof(double);                                         \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, nrows, D, yb0, pl->stride, tboff,                  \
-                       nch, Cs, out, acc, sp.nsplit, sp.ndt);                                         \
-  } while (0)
   if (pl->large) {   // one pass per slice of 64 harmonics, accumulating into out
-    for (int sl = 0; sl < pl->nslice; ++sl) TEMX_LR(16, 16 * sl, C + (int64_t)64 * sl * D, sl > 0 ? 1 : 0);
-  } else {
-    switch (pl->TB) {
-      case 4: TEMX_LR(4, 0, C, 0); break;
-      case 8: TEMX_LR(8, 0, C, 0); break;
-      case 13: TEMX_LR(13, 0, C, 0); break;
-      default: TEMX_LR(16, 0, C, 0); break;
-    }
+    for (int sl = 0; sl < pl->nslice; ++sl)
+      hipLaunchKernelGGL(recon_kernel<16>, grid, block, (size_t)4 * 16 * 64 * sizeof(double), st, nrows, D, yb0, pl->stride,
+          16 * sl, nch, C + (int64_t)64 * sl * D, out, sl > 0 ? 1 : 0, sp.nsplit, sp.ndt);
+    HIPCHK(hipGetLastError());
+    return TEMX_OK;
   }
-#undef TEMX_LR
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return dispatch(TBValues{}, pl->TB, [&](auto tb) {
+    constexpr int TBv = decltype(tb)::value;
+    return launch<recon_kernel<TBv>>(grid, block, (size_t)4 * TBv * 64 * sizeof(double), st, nrows, D, yb0, pl->stride, 0,
+        nch, C, out, 0, sp.nsplit, sp.ndt);
+  });
 }
 
 // B[NF][K][D] = Y0^T {fields}: one projection sweep, or one per slice of 64 harmonics (large L)
@@ -673,79 +632,55 @@ constexpr int cls_proj_pd(bool op, int nfw) {
             : (nfw == 1 ? (f32 ? TEMX_CLS_E_PD_F32 : CLS_PROJ_E_PD) : (f32 ? TEMX_CLS_Q_PD_F32 : 2));
 }
 
-template <typename T, int NF>
-static int launch_project_cls_t(temx_plan* pl, const FieldPtrs<NF>& fp, int64_t D, const double* colscale,
-                                int sfield, double* partial, const Split& sp, hipStream_t st) {
-  const int2* cuts = nullptr;
-  if (int rc = class_cuts_dev(pl, sp.nsplit, &cuts)) return rc;
-  dim3 grid(sp.grid), block(256);
-#define TEMX_LPC(TBSv, NFWv, WPSv, OPv)                                                             \
-  hipLaunchKernelGGL((project_cls_kernel<T, NF, NFWv, TBSv, WPSv, cls_proj_pd<T>(OPv, NFWv), OPv>), grid, block, 0, st, fp, D, pl->K, \
-                     pl->ycls.d(), static_cast<const int4*>(pl->crow.p), cuts, colscale, sfield,    \
-                     partial, sp.nsplit, sp.ndt, (double*)nullptr)
-  if (NF == 1 || sp.dpw == 1) {     // one field per wave (NF = 4: small ragged D, one d-tile per workgroup)
-    switch (pl->TBS) {
-      case 2: TEMX_LPC(2, 1, CLS_PROJ_E_WPS, false); break;
-      case 4: TEMX_LPC(4, 1, CLS_PROJ_E_WPS, false); break;
-      case 7: TEMX_LPC(7, 1, CLS_PROJ_E_WPS, false); break;
-      default: TEMX_LPC(8, 1, CLS_PROJ_E_WPS, false); break;
-    }
-  } else {
-    switch (pl->TBS) {
-      case 2: TEMX_LPC(2, NF, 2, false); break;
-      case 4: TEMX_LPC(4, NF, 2, false); break;
-      case 7: TEMX_LPC(7, NF, 2, false); break;
-      default: TEMX_LPC(8, NF, 2, false); break;
-    }
-  }
-#undef TEMX_LPC
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
-}
-
 template <int NF>
 static int launch_project_cls(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int64_t D,
                               const double* colscale, int sfield, double* partial, const Split& sp,
                               hipStream_t st) {
-  if (dtype == TEMX_F64) return launch_project_cls_t<double, NF>(pl, fp, D, colscale, sfield, partial, sp, st);
-  if (dtype == TEMX_F32) return launch_project_cls_t<float, NF>(pl, fp, D, colscale, sfield, partial, sp, st);
-  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  return by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    const int2* cuts = nullptr;
+    if (int rc = class_cuts_dev(pl, sp.nsplit, &cuts)) return rc;
+    auto go = [&](auto nfw, auto wps) {
+      return dispatch(TBSValues{}, pl->TBS, [&](auto tbs) {
+        constexpr int NFW = decltype(nfw)::value, WPS = decltype(wps)::value;
+        return launch<project_cls_kernel<T, NF, NFW, decltype(tbs)::value, WPS, cls_proj_pd<T>(false, NFW), false>>(
+            dim3(sp.grid), dim3(256), 0, st, fp, D, pl->K, pl->ycls.d(), static_cast<const int4*>(pl->crow.p), cuts, colscale,
+            sfield, partial, sp.nsplit, sp.ndt, (double*)nullptr);
+      });
+    };
+    // one field per wave (NF = 4: small ragged D, one d-tile per workgroup), or all of them
+    return NF == 1 || sp.dpw == 1 ? go(Int<1>{}, Int<CLS_PROJ_E_WPS>{}) : go(Int<NF>{}, Int<2>{});
+  });
 }
 
-template <typename T, int KIND>
-static int launch_sweep_op_t(temx_plan* pl, const FieldPtrs<4>& fp, double* partial, const Split& sp, double* sums,
-                             hipStream_t st) {
-  const int2* cuts = nullptr;
-  if (int rc = class_cuts_dev(pl, sp.nsplit, &cuts, true)) return rc;
-  dim3 grid(sp.grid), block(256);
-  // the tracer sweep (42 accumulators) runs two waves per SIMD: a ring of 2 batches keeps it inside 256 registers
-  constexpr int PDv = KIND == 1 ? (sizeof(T) == 4 ? 4 : 2) : (sizeof(T) == 4 ? TEMX_CLS_OP_PD_F32 : TEMX_CLS_OP_PD);
-  // loads of 1 row x 64 columns (sweep_opr_kernel, kernels_op2.hpp) unless the last workgroup column would be
-  // mostly padding (D = 72: 64 + 8) or TEMX_OP_MAP=tile asks for the tile form (A/B)
-  const int64_t wcols = (pl->D + 63) / 64 * 64;
-  // fp64 only: with fp32 inputs the tile form measured faster (ne240 x 128 x 1: 1.77 vs 2.08 ms, ne120 x 72 x 30: 7.2 vs 7.5)
-  const bool row_map = sizeof(T) == 8 && !pl->op_tile && wcols * 100 <= pl->D * 115;
-  constexpr int PDr = 2;
-#define TEMX_LSO(TBSv)                                                                                \
-  do {                                                                                                \
-    if (row_map)                                                                                      \
-      hipLaunchKernelGGL((sweep_opr_kernel<double, TBSv, PDr, KIND>), grid, block, 0, st, fp, pl->D, pl->K, pl->ycls.d(), \
-                         static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(), partial, sp.nsplit,  \
-                         sp.ndt, sums);                                                               \
-    else                                                                                              \
-      hipLaunchKernelGGL((sweep_op_kernel<T, TBSv, PDv, KIND>), grid, block, 0, st, fp, pl->D, pl->K, pl->ycls.d(), \
-                         static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(), partial, sp.nsplit,   \
-                         sp.ndt, sums);                                                               \
-  } while (0)
-  switch (pl->TBS) {
-    case 2: TEMX_LSO(2); break;
-    case 4: TEMX_LSO(4); break;
-    case 7: TEMX_LSO(7); break;
-    default: TEMX_LSO(8); break;
-  }
-#undef TEMX_LSO
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+// KIND 0: (u, v, T, omega) -> csum; KIND 1: (q, v, omega) -> csq
+template <int KIND>
+static int launch_sweep_op(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double* partial, const Split& sp,
+                           hipStream_t st) {
+  double* sums = KIND == 0 ? pl->csum.d() : pl->csq.d();
+  return by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    const int2* cuts = nullptr;
+    if (int rc = class_cuts_dev(pl, sp.nsplit, &cuts, true)) return rc;
+    dim3 grid(sp.grid), block(256);
+    // the tracer sweep (42 accumulators) runs two waves per SIMD: a ring of 2 batches keeps it inside 256 registers
+    constexpr int PDv = KIND == 1 ? (sizeof(T) == 4 ? 4 : 2) : (sizeof(T) == 4 ? TEMX_CLS_OP_PD_F32 : TEMX_CLS_OP_PD);
+    // loads of 1 row x 64 columns (sweep_opr_kernel, kernels_op2.hpp) unless the last workgroup column would be
+    // mostly padding (D = 72: 64 + 8) or TEMX_OP_MAP=tile asks for the tile form (A/B)
+    const int64_t wcols = (pl->D + 63) / 64 * 64;
+    // fp64 only: with fp32 inputs the tile form measured faster (ne240 x 128 x 1: 1.77 vs 2.08 ms, ne120 x 72 x 30: 7.2 vs 7.5)
+    const bool row_map = sizeof(T) == 8 && !pl->op_tile && wcols * 100 <= pl->D * 115;
+    constexpr int PDr = 2;
+    return dispatch(TBSValues{}, pl->TBS, [&](auto tbs) {
+      constexpr int TBSv = decltype(tbs)::value;
+      if (row_map)
+        return launch<sweep_opr_kernel<double, TBSv, PDr, KIND>>(grid, block, 0, st, fp, pl->D, pl->K, pl->ycls.d(),
+                                                                 static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(),
+                                                                 partial, sp.nsplit, sp.ndt, sums);
+      return launch<sweep_op_kernel<T, TBSv, PDv, KIND>>(grid, block, 0, st, fp, pl->D, pl->K, pl->ycls.d(),
+          static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(), partial, sp.nsplit, sp.ndt, sums);
+    });
+  });
 }
 
 // TEM + one tracer in one sweep (kernels_op2.hpp): (u, v, T, omega, q) -> csum, csq, 10 slabs per split
@@ -755,101 +690,41 @@ static int launch_sweep_opw2_t(temx_plan* pl, const FieldPtrs<5>& fp, double* pa
   if (int rc = class_cuts_dev(pl, sp.nsplit * 4, &cuts, true)) return rc;
   dim3 grid(sp.grid), block(256);
   constexpr int PDv = sizeof(T) == 4 ? TEMX_CLS_OP_PD_F32 : TEMX_CLS_OP_PD;
-#define TEMX_LSW(TBSv)                                                                                       \
-  hipLaunchKernelGGL((sweep_opw_kernel<T, TBSv, PDv, 2>), grid, block, 0, st, fp, pl->D, pl->K, pl->ycls.d(), \
-                     static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(), partial, sp.nsplit, sp.ndt, \
-                     pl->csum.d(), pl->csq.d())
-  switch (pl->TBS) {
-    case 2: TEMX_LSW(2); break;
-    case 4: TEMX_LSW(4); break;
-    case 7: TEMX_LSW(7); break;
-    default: TEMX_LSW(8); break;
-  }
-#undef TEMX_LSW
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
-}
-
-// KIND 0: (u, v, T, omega) -> csum; KIND 1: (q, v, omega) -> csq
-template <int KIND>
-static int launch_sweep_op(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double* partial, const Split& sp,
-                           hipStream_t st) {
-  double* sums = KIND == 0 ? pl->csum.d() : pl->csq.d();
-  if (dtype == TEMX_F64) return launch_sweep_op_t<double, KIND>(pl, fp, partial, sp, sums, st);
-  if (dtype == TEMX_F32) return launch_sweep_op_t<float, KIND>(pl, fp, partial, sp, sums, st);
-  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
-}
-
-template <typename T, int MODE, int DPW, int KIND>
-static int launch_eddy_cls_d(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
-                             const Split& sp, const EddyOut& eo, hipStream_t st) {
-  const int2* cuts = nullptr;
-  if (int rc = class_cuts_dev(pl, sp.nsplit * (8 / DPW), &cuts)) return rc;
-  dim3 grid(sp.grid), block(512);
-  constexpr int NFR = KIND == 0 ? 4 : 3;
-#define TEMX_LEC(TBSv)                                                                                \
-  do {                                                                                                \
-    auto kern = eddy_cls_kernel<T, TBSv, MODE, DPW, KIND>;                                            \
-    const size_t lds = ((size_t)DPW * NFR * 2 * TBSv * 64 + 8 * 2 * TBSv * 16) * sizeof(double);      \
-    static std::atomic<uint64_t> attr_set{0};                                                         \
-    if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) \
-      return rc_;                                                                                     \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, fp, pl->D, pl->K, pl->K4, pl->ycls.d(),            \
-                       static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(), C, partial,      \
-                       sp.nsplit, sp.ndt, eo);                                                        \
-  } while (0)
-  switch (pl->TBS) {
-    case 2: TEMX_LEC(2); break;
-    case 4: TEMX_LEC(4); break;
-    case 7: TEMX_LEC(7); break;
-    default: TEMX_LEC(8); break;
-  }
-#undef TEMX_LEC
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return dispatch(TBSValues{}, pl->TBS, [&](auto tbs) {
+    return launch<sweep_opw_kernel<T, decltype(tbs)::value, PDv, 2>>(grid, block, 0, st, fp, pl->D, pl->K, pl->ycls.d(),
+        static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(), partial, sp.nsplit, sp.ndt, pl->csum.d(),
+        pl->csq.d());
+  });
 }
 
 template <typename T, int MODE, int KIND>
 static int launch_eddy_cls_t(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
                              const Split& sp, const EddyOut& eo, hipStream_t st) {
-  switch (sp.dpw) {
-    case 1: return launch_eddy_cls_d<T, MODE, 1, KIND>(pl, fp, C, partial, sp, eo, st);
-    case 2: return launch_eddy_cls_d<T, MODE, 2, KIND>(pl, fp, C, partial, sp, eo, st);
-    default: return launch_eddy_cls_d<T, MODE, 4, KIND>(pl, fp, C, partial, sp, eo, st);
-  }
-}
-
-template <int DPW, int KIND>
-static int launch_flux_cls_d(temx_plan* pl, const double* C, double* partial, const Split& sp, hipStream_t st) {
-  dim3 grid(sp.grid), block(512);
-#define TEMX_LFC(TBSv)                                                                                \
-  do {                                                                                                \
-    auto kern = flux_cls_kernel<TBSv, DPW, KIND>;                                                     \
-    const size_t lds = ((size_t)DPW * 4 * 2 * TBSv * 64 + 8 * 2 * TBSv * 16) * sizeof(double);        \
-    static std::atomic<uint64_t> attr_set{0};                                                         \
-    if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) \
-      return rc_;                                                                                     \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, pl->D, pl->K, pl->K4, pl->ycls.d(), pl->csum.d(),  \
-                       pl->csq.d(), pl->ccnt.d(), pl->cgroups, C, partial, sp.nsplit, sp.ndt);        \
-  } while (0)
-  switch (pl->TBS) {
-    case 2: TEMX_LFC(2); break;
-    case 4: TEMX_LFC(4); break;
-    case 7: TEMX_LFC(7); break;
-    default: TEMX_LFC(8); break;
-  }
-#undef TEMX_LFC
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  constexpr int NFR = KIND == 0 ? 4 : 3;
+  return dispatch(DpwValues{}, sp.dpw, [&](auto dpw) {
+    constexpr int DPW = decltype(dpw)::value;
+    const int2* cuts = nullptr;
+    if (int rc = class_cuts_dev(pl, sp.nsplit * (8 / DPW), &cuts)) return rc;
+    return dispatch(TBSValues{}, pl->TBS, [&](auto tbs) {
+      constexpr int TBSv = decltype(tbs)::value;
+      const size_t lds = ((size_t)DPW * NFR * 2 * TBSv * 64 + 8 * 2 * TBSv * 16) * sizeof(double);
+      return launch_lds<eddy_cls_kernel<T, TBSv, MODE, DPW, KIND>>(pl->device, dim3(sp.grid), dim3(512), lds, st, fp, pl->D,
+          pl->K, pl->K4, pl->ycls.d(), static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(), C, partial, sp.nsplit,
+          sp.ndt, eo);
+    });
+  });
 }
 
 template <int KIND>
 static int launch_flux_cls(temx_plan* pl, const double* C, double* partial, const Split& sp, hipStream_t st) {
-  switch (sp.dpw) {
-    case 1: return launch_flux_cls_d<1, KIND>(pl, C, partial, sp, st);
-    case 2: return launch_flux_cls_d<2, KIND>(pl, C, partial, sp, st);
-    default: return launch_flux_cls_d<4, KIND>(pl, C, partial, sp, st);
-  }
+  return dispatch(DpwValues{}, sp.dpw, [&](auto dpw) {
+    return dispatch(TBSValues{}, pl->TBS, [&](auto tbs) {
+      constexpr int DPW = decltype(dpw)::value, TBSv = decltype(tbs)::value;
+      const size_t lds = ((size_t)DPW * 4 * 2 * TBSv * 64 + 8 * 2 * TBSv * 16) * sizeof(double);
+      return launch_lds<flux_cls_kernel<TBSv, DPW, KIND>>(pl->device, dim3(sp.grid), dim3(512), lds, st, pl->D, pl->K,
+          pl->K4, pl->ycls.d(), pl->csum.d(), pl->csq.d(), pl->ccnt.d(), pl->cgroups, C, partial, sp.nsplit, sp.ndt);
+    });
+  });
 }
 
 // ---- large-L class path ----------------------------------------------------------------------------
@@ -859,16 +734,12 @@ static int launch_class_sums(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, h
   const int2* cuts = nullptr;
   if (int rc = class_cuts_dev(pl, sp.nsplit, &cuts, true)) return rc;
   dim3 grid(sp.grid), block(256);
-#define TEMX_LCS(Tv)                                                                                  \
-  hipLaunchKernelGGL((project_cls_kernel<Tv, 4, 4, 2, TEMX_CLS_OP_WPS, cls_proj_pd<Tv>(true, 4), true, false>), grid, block, 0, st, \
-                     fp, pl->D, pl->K, (const double*)nullptr, static_cast<const int4*>(pl->crow.p), cuts,          \
-                     pl->colscale.d(), 2, (double*)nullptr, sp.nsplit, sp.ndt, pl->csum.d())
-  if (dtype == TEMX_F64) TEMX_LCS(double);
-  else if (dtype == TEMX_F32) TEMX_LCS(float);
-  else return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
-#undef TEMX_LCS
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch<project_cls_kernel<T, 4, 4, 2, TEMX_CLS_OP_WPS, cls_proj_pd<T>(true, 4), true, false>>(grid, block, 0,
+        st, fp, pl->D, pl->K, (const double*)nullptr, static_cast<const int4*>(pl->crow.p), cuts, pl->colscale.d(), 2,
+        (double*)nullptr, sp.nsplit, sp.ndt, pl->csum.d());
+  });
 }
 
 // B[NQ][K][D] = sum over classes of Y_l (S_N +- S_S) for NQ sums of the records in rec, slice by slice
@@ -880,23 +751,14 @@ static int project_sums(temx_plan* pl, const double* rec, int RS, int row0, doub
   int rc;
   for (int sl = 0; sl < pl->nslice; ++sl) {
     const int Ks = std::min(64, pl->K - 64 * sl);
-#define TEMX_LSP(DPWv)                                                                                \
-  do {                                                                                                \
-    auto kern = sums_project_kernel<NQ, DPWv>;                                                        \
-    const size_t lds = ((size_t)DPWv * NQ * 16 * 64 + 8 * 256) * sizeof(double);                      \
-    static std::atomic<uint64_t> attr_set{0};                                                         \
-    if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) \
-      return rc_;                                                                                     \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, D, pl->K, 64 * sl, pl->ycls_l.d() + sl * pl->ycls_lstride, \
-                       rec, RS, row0, pl->cgroups, pl->partial.d(), sp.nsplit, sp.ndt);               \
-  } while (0)
-    switch (sp.dpw) {
-      case 1: TEMX_LSP(1); break;
-      case 2: TEMX_LSP(2); break;
-      default: TEMX_LSP(4); break;
-    }
-#undef TEMX_LSP
-    HIPCHK(hipGetLastError());
+    rc = dispatch(DpwValues{}, sp.dpw, [&](auto dpw) {
+      constexpr int DPW = decltype(dpw)::value;
+      const size_t lds = ((size_t)DPW * NQ * 16 * 64 + 8 * 256) * sizeof(double);
+      return launch_lds<sums_project_kernel<NQ, DPW>>(pl->device, grid, block, lds, st, D, pl->K, 64 * sl,
+                                                      pl->ycls_l.d() + sl * pl->ycls_lstride, rec, RS, row0, pl->cgroups,
+                                                      pl->partial.d(), sp.nsplit, sp.ndt);
+    });
+    if (rc) return rc;
     if ((rc = launch_reduce(pl, pl->partial.d(), sp.nsplit, (int64_t)NQ * Ks * D, pl->Bs.d(), st))) return rc;
     for (int q = 0; q < NQ; ++q)
       HIPCHK(hipMemcpyAsync(B + ((int64_t)q * pl->K + 64 * sl) * D, pl->Bs.d() + (int64_t)q * Ks * D,
@@ -908,98 +770,45 @@ static int project_sums(temx_plan* pl, const double* rec, int RS, int row0, doub
 static int launch_flux_large(temx_plan* pl, const double* C, hipStream_t st) {
   const Split& sp = pl->sp_lflux;
   dim3 grid(sp.grid), block(512);
-#define TEMX_LFL(NSv)                                                                                 \
-  do {                                                                                                \
-    auto kern = flux_large_kernel<NSv>;                                                               \
-    const size_t lds = ((size_t)NSv * 4 * 16 * 64 + 8 * 256) * sizeof(double);                        \
-    static std::atomic<uint64_t> attr_set{0};                                                         \
-    if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) \
-      return rc_;                                                                                     \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, pl->D, pl->K, pl->K4, pl->ycls_l.d(), pl->ycls_lstride, \
-                       pl->csum.d(), pl->ccnt.d(), pl->cgroups, C, pl->pbuf.d(), sp.nsplit, sp.ndt);  \
-  } while (0)
-  switch (pl->nslice) {
-    case 2: TEMX_LFL(2); break;
-    case 3: TEMX_LFL(3); break;
-    default: TEMX_LFL(4); break;
-  }
-#undef TEMX_LFL
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
-}
-
-template <typename T, int NF>
-static int launch_project_sym_t(temx_plan* pl, const FieldPtrs<NF>& fp, int64_t D, const double* colscale,
-                                int sfield, double* partial, const Split& sp, hipStream_t st) {
-  dim3 grid(sp.grid), block(256);
-#define TEMX_LPS(TBSv, NFWv, WPSv)                                                                  \
-  hipLaunchKernelGGL((project_sym_kernel<T, NF, NFWv, TBSv, WPSv>), grid, block, 0, st, fp, D, pl->K, \
-                     pl->ysym.d(), static_cast<const int*>(pl->rows.p), pl->npg, pl->npg_alloc * 4, \
-                     colscale, sfield, partial, sp.nsplit, sp.ndt)
-  if (NF == 4 && sp.dpw == 1) {     // small ragged D: one d-tile per workgroup, one field per wave
-    switch (pl->TBS) {
-      case 2: TEMX_LPS(2, 1, SYM_PROJ_E_WPS); break;
-      case 4: TEMX_LPS(4, 1, SYM_PROJ_E_WPS); break;
-      case 7: TEMX_LPS(7, 1, SYM_PROJ_E_WPS); break;
-      default: TEMX_LPS(8, 1, SYM_PROJ_E_WPS); break;
-    }
-  } else {
-    switch (pl->TBS) {
-      case 2: TEMX_LPS(2, NF, 2); break;
-      case 4: TEMX_LPS(4, NF, 2); break;
-      case 7: TEMX_LPS(7, NF, 2); break;
-      default: TEMX_LPS(8, NF, 2); break;
-    }
-  }
-#undef TEMX_LPS
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return dispatch(SliceValues{}, pl->nslice, [&](auto ns) {
+    constexpr int NS = decltype(ns)::value;
+    const size_t lds = ((size_t)NS * 4 * 16 * 64 + 8 * 256) * sizeof(double);
+    return launch_lds<flux_large_kernel<NS>>(pl->device, grid, block, lds, st, pl->D, pl->K, pl->K4, pl->ycls_l.d(),
+        pl->ycls_lstride, pl->csum.d(), pl->ccnt.d(), pl->cgroups, C, pl->pbuf.d(), sp.nsplit, sp.ndt);
+  });
 }
 
 template <int NF>
 static int launch_project_sym(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int64_t D,
                               const double* colscale, int sfield, double* partial, const Split& sp,
                               hipStream_t st) {
-  if (dtype == TEMX_F64) return launch_project_sym_t<double, NF>(pl, fp, D, colscale, sfield, partial, sp, st);
-  if (dtype == TEMX_F32) return launch_project_sym_t<float, NF>(pl, fp, D, colscale, sfield, partial, sp, st);
-  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
-}
-
-template <typename T, int MODE, int DPW, int KIND>
-static int launch_eddy_sym_d(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
-                             const Split& sp, const EddyOut& eo, hipStream_t st) {
-  dim3 grid(sp.grid), block(512);
-  constexpr int NFR = KIND == 0 ? 4 : 3;
-#define TEMX_LES(TBSv)                                                                                \
-  do {                                                                                                \
-    auto kern = eddy_sym_kernel<T, TBSv, MODE, DPW, KIND>;                                            \
-    const size_t lds = ((size_t)DPW * NFR * 2 * TBSv * 64 + 8 * 2 * TBSv * 16) * sizeof(double);      \
-    static std::atomic<uint64_t> attr_set{0};   /* per instantiation, one bit per device */           \
-    if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) \
-      return rc_;                                                                                     \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, fp, pl->D, pl->K, pl->K4, pl->ysym.d(),            \
-                       static_cast<const int*>(pl->rows.p), pl->npg, pl->npg_alloc * 4, pl->npair,    \
-                       pl->colscale.d(), C, partial, sp.nsplit, sp.ndt, eo);                          \
-  } while (0)
-  switch (pl->TBS) {
-    case 2: TEMX_LES(2); break;
-    case 4: TEMX_LES(4); break;
-    case 7: TEMX_LES(7); break;
-    default: TEMX_LES(8); break;
-  }
-#undef TEMX_LES
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto go = [&](auto nfw, auto wps) {
+      return dispatch(TBSValues{}, pl->TBS, [&](auto tbs) {
+        return launch<project_sym_kernel<T, NF, decltype(nfw)::value, decltype(tbs)::value, decltype(wps)::value>>(
+            dim3(sp.grid), dim3(256), 0, st, fp, D, pl->K, pl->ysym.d(), static_cast<const int*>(pl->rows.p), pl->npg,
+            pl->npg_alloc * 4, colscale, sfield, partial, sp.nsplit, sp.ndt);
+      });
+    };
+    // small ragged D: one d-tile per workgroup, one field per wave
+    return NF == 4 && sp.dpw == 1 ? go(Int<1>{}, Int<SYM_PROJ_E_WPS>{}) : go(Int<NF>{}, Int<2>{});
+  });
 }
 
 template <typename T, int MODE, int KIND>
 static int launch_eddy_sym_t(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
                              const Split& sp, const EddyOut& eo, hipStream_t st) {
-  switch (sp.dpw) {
-    case 1: return launch_eddy_sym_d<T, MODE, 1, KIND>(pl, fp, C, partial, sp, eo, st);
-    case 2: return launch_eddy_sym_d<T, MODE, 2, KIND>(pl, fp, C, partial, sp, eo, st);
-    default: return launch_eddy_sym_d<T, MODE, 4, KIND>(pl, fp, C, partial, sp, eo, st);
-  }
+  constexpr int NFR = KIND == 0 ? 4 : 3;
+  return dispatch(DpwValues{}, sp.dpw, [&](auto dpw) {
+    return dispatch(TBSValues{}, pl->TBS, [&](auto tbs) {
+      constexpr int DPW = decltype(dpw)::value, TBSv = decltype(tbs)::value;
+      const size_t lds = ((size_t)DPW * NFR * 2 * TBSv * 64 + 8 * 2 * TBSv * 16) * sizeof(double);
+      return launch_lds<eddy_sym_kernel<T, TBSv, MODE, DPW, KIND>>(pl->device, dim3(sp.grid), dim3(512), lds, st, fp, pl->D,
+          pl->K, pl->K4, pl->ysym.d(), static_cast<const int*>(pl->rows.p), pl->npg, pl->npg_alloc * 4, pl->npair,
+          pl->colscale.d(), C, partial, sp.nsplit, sp.ndt, eo);
+    });
+  });
 }
 
 // The fused second sweep reads ONE set of Y0 blocks for the reconstruction and for the projection, so it
@@ -1021,34 +830,18 @@ static inline bool sym_project(const temx_plan* pl, int nf) {   // paired projec
 template <int KIND>
 static int run_eddy(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, const double* C, double* partial,
                     const EddyOut* eo, hipStream_t st) {
-  EddyOut none{};
-  if (pl->cls) {
-    if (dtype == TEMX_F64)
-      return eo ? launch_eddy_cls_t<double, 1, KIND>(pl, fp, C, partial, pl->sp_ceddy, *eo, st)
-                : launch_eddy_cls_t<double, 0, KIND>(pl, fp, C, partial, pl->sp_ceddy, none, st);
-    if (dtype == TEMX_F32)
-      return eo ? launch_eddy_cls_t<float, 1, KIND>(pl, fp, C, partial, pl->sp_ceddy, *eo, st)
-                : launch_eddy_cls_t<float, 0, KIND>(pl, fp, C, partial, pl->sp_ceddy, none, st);
-    return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
-  }
-  if (pl->sym) {
-    if (dtype == TEMX_F64)
-      return eo ? launch_eddy_sym_t<double, 1, KIND>(pl, fp, C, partial, pl->sp_seddy, *eo, st)
-                : launch_eddy_sym_t<double, 0, KIND>(pl, fp, C, partial, pl->sp_seddy, none, st);
-    if (dtype == TEMX_F32)
-      return eo ? launch_eddy_sym_t<float, 1, KIND>(pl, fp, C, partial, pl->sp_seddy, *eo, st)
-                : launch_eddy_sym_t<float, 0, KIND>(pl, fp, C, partial, pl->sp_seddy, none, st);
-    return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
-  }
-  if (dtype == TEMX_F64) {
-    return eo ? launch_eddy_t<double, 1, KIND>(pl, fp, C, partial, pl->sp_eddy, *eo, st)
-              : launch_eddy_t<double, 0, KIND>(pl, fp, C, partial, pl->sp_eddy, none, st);
-  }
-  if (dtype == TEMX_F32) {
-    return eo ? launch_eddy_t<float, 1, KIND>(pl, fp, C, partial, pl->sp_eddy, *eo, st)
-              : launch_eddy_t<float, 0, KIND>(pl, fp, C, partial, pl->sp_eddy, none, st);
-  }
-  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  const EddyOut none{};
+  return by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto go = [&](auto mode) {       // MODE 1: the sweep also writes the native eddy fields *eo
+      constexpr int MODE = decltype(mode)::value;
+      const EddyOut& o = MODE ? *eo : none;
+      if (pl->cls) return launch_eddy_cls_t<T, MODE, KIND>(pl, fp, C, partial, pl->sp_ceddy, o, st);
+      if (pl->sym) return launch_eddy_sym_t<T, MODE, KIND>(pl, fp, C, partial, pl->sp_seddy, o, st);
+      return launch_eddy_t<T, MODE, KIND>(pl, fp, C, partial, pl->sp_eddy, o, st);
+    };
+    return eo ? go(Int<1>{}) : go(Int<0>{});
+  });
 }
 
 static FieldPtrs<4> four(const void* a, const void* b, const void* c, const void* d) {
@@ -1194,58 +987,46 @@ static int launch_sweep_os_t(temx_plan* pl, const FieldPtrs<4>& fp, bool sub, co
   // (the reference pre-pass needs the first KR rows of px only: pp == NULL tells the kernels to store nothing else --
   //  146 x 8 B per lane and workgroup otherwise, 150 MB at ne120 x 72 x 30 for a sweep that reads 240 MB)
   double* pp = sub ? nullptr : partial + (int64_t)sp.nsplit * KD::NFX * pl->KX * pl->D;
-#define TEMX_LOS(TBSv, TBXv)                                                                                        \
-  do {                                                                                                              \
-    if constexpr (KIND == 3) {                                                                                      \
-      if (tile_map) return fail(TEMX_EUNSUPPORTED, "two tracers per sweep: row-map sweeps only");                   \
-    }                                                                                                               \
-    if constexpr (KIND != 3) if (tile_map) {                                                                        \
-      auto kern = sweep_os_kernel<T, TBSv, TBXv, NBR, PDv, KIND, DF>;                                               \
-      const size_t lds = ((size_t)4 * (DF ? 2 : 1) * 2 * TBXv * 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +            \
-                          (size_t)4 * KD::NP * 2 * TBSv * 64) * 8;                                                  \
-      static std::atomic<uint64_t> attr_set{0};                                                                     \
-      if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) return rc_; \
-      hipLaunchKernelGGL(kern, grid, block, lds, st, fp, pl->D, pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(),   \
-                         static_cast<const int4*>(sub ? pl->crow_s.p : pl->crow.p), cuts, pl->colscale.d(), rho,    \
-                         pl->KR, px, pp, sp.nsplit, sp.ndt);                                                        \
-      break;                                                                                                        \
-    }                                                                                                               \
-    if (sizeof(T) == 4) {   /* fp32 inputs: two waves per SIMD (kernels_op2.hpp, sweep_os2_kernel) */              \
-      if (pl->cls_max_side > 8 * TEMX_F32_SIDE_CAP)                                                                 \
-        return fail(TEMX_EUNSUPPORTED, "single sweep of fp32 fields: a latitude class of this plan has %lld members on one " \
-                    "side, and the sweep sums a side in fp32; create the plan with TEMX_LAT_TOL_F32",               \
-                    (long long)pl->cls_max_side);                                                                   \
-      auto kern = sweep_os2_kernel<float, TBSv, TBXv, NBR, 2, KIND>;                                                \
-      const size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +                      \
-                          (size_t)8 * (KD::NP - KD::NPR) * TBSv * 64 + (size_t)(KD::NF + KD::NP) * 512) * 8;        \
-      static std::atomic<uint64_t> attr_set{0};                                                                     \
-      if (int rc_ = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(kern), (int)lds)) return rc_; \
-      const int si = sub ? 1 : 0;                                                                                   \
-      hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, fp, pl->D, pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(), \
-                         static_cast<const int4*>(pl->side_crow[si][0].p), static_cast<const int4*>(pl->side_crow[si][1].p), \
-                         static_cast<const int*>(pl->side_gfirst[si][0].p), static_cast<const int*>(pl->side_gfirst[si][1].p), \
-                         cuts, pl->colscale.d(), rho, pl->KR, px, pp, sp.nsplit, sp.ndt);                           \
-    } else {                                                                                                        \
-      /* Y blocks x 2 | counts | reference operands | product accumulators | exchange | the flag form's two counters */ \
-      constexpr size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +                  \
-                              (size_t)4 * (KD::NP - KD::NPR) * 2 * TBSv * 64 + (size_t)2 * (KD::NF + KD::NP) * 256 + 2) * 8; \
-      static_assert(lds <= 163840, "the single sweep's workgroup fits the LDS of a compute unit");                 \
-      auto kern = pl->os_barrier ? sweep_osr_kernel<double, TBSv, TBXv, NBR, 2, KIND, 0>                            \
-                                 : sweep_osr_kernel<double, TBSv, TBXv, NBR, 2, KIND, 1>;                           \
-      static std::atomic<uint64_t> attr_set[2] = {{0}, {0}};                                                        \
-      if (int rc_ = lds_attr_once(attr_set[pl->os_barrier ? 0 : 1], pl->device, reinterpret_cast<const void*>(kern), (int)lds)) return rc_; \
-      hipLaunchKernelGGL(kern, grid, block, lds, st, fp, pl->D, pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(),   \
-                         static_cast<const int4*>(sub ? pl->crow_s.p : pl->crow.p), cuts, pl->colscale.d(), rho,    \
-                         pl->KR, px, pp, sp.nsplit, sp.ndt, static_cast<int*>(pl->flag.p) + 1);                     \
-    }                                                                                                               \
-  } while (0)
-  if (pl->TBS == 7 && pl->TBX == 13) TEMX_LOS(7, 13);
-  else if (pl->TBS == 4 && pl->TBX == 8) TEMX_LOS(4, 8);
-  else if (pl->TBS == 2 && pl->TBX == 4) TEMX_LOS(2, 4);
-  else return fail(TEMX_EUNSUPPORTED, "single-sweep form: no instantiation for L = %d", pl->L);
-#undef TEMX_LOS
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  int rc = TEMX_OK;
+  const bool listed = dispatch_strict(OsPairs{}, pl->TBS, pl->TBX, rc, [&](auto pair) {
+    constexpr int TBSv = decltype(pair)::first, TBXv = decltype(pair)::second;
+    if constexpr (KIND == 3) {
+      if (tile_map) return fail(TEMX_EUNSUPPORTED, "two tracers per sweep: row-map sweeps only");
+    }
+    if constexpr (KIND != 3) if (tile_map) {
+      const size_t lds = ((size_t)4 * (DF ? 2 : 1) * 2 * TBXv * 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +
+                          (size_t)4 * KD::NP * 2 * TBSv * 64) * 8;
+      return launch_lds<sweep_os_kernel<T, TBSv, TBXv, NBR, PDv, KIND, DF>>(pl->device, grid, block, lds, st, fp, pl->D,
+          pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(), static_cast<const int4*>(sub ? pl->crow_s.p : pl->crow.p), cuts,
+          pl->colscale.d(), rho, pl->KR, px, pp, sp.nsplit, sp.ndt);
+    }
+    if (sizeof(T) == 4) {   // fp32 inputs: two waves per SIMD (kernels_op2.hpp, sweep_os2_kernel)
+      if (pl->cls_max_side > 8 * TEMX_F32_SIDE_CAP)
+        return fail(TEMX_EUNSUPPORTED, "single sweep of fp32 fields: a latitude class of this plan has %lld members on one "
+                    "side, and the sweep sums a side in fp32; create the plan with TEMX_LAT_TOL_F32",
+                    (long long)pl->cls_max_side);
+      const size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +
+                          (size_t)8 * (KD::NP - KD::NPR) * TBSv * 64 + (size_t)(KD::NF + KD::NP) * 512) * 8;
+      const int si = sub ? 1 : 0;
+      return launch_lds<sweep_os2_kernel<float, TBSv, TBXv, NBR, 2, KIND>>(
+          pl->device, grid, dim3(512), lds, st, fp, pl->D, pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(),
+          static_cast<const int4*>(pl->side_crow[si][0].p), static_cast<const int4*>(pl->side_crow[si][1].p),
+          static_cast<const int*>(pl->side_gfirst[si][0].p), static_cast<const int*>(pl->side_gfirst[si][1].p),
+          cuts, pl->colscale.d(), rho, pl->KR, px, pp, sp.nsplit, sp.ndt);
+    }
+    // Y blocks x 2 | counts | reference operands | product accumulators | exchange | the flag form's two counters
+    constexpr size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +
+                            (size_t)4 * (KD::NP - KD::NPR) * 2 * TBSv * 64 + (size_t)2 * (KD::NF + KD::NP) * 256 + 2) * 8;
+    static_assert(lds <= 163840, "the single sweep's workgroup fits the LDS of a compute unit");
+    auto go = [&](auto handoff) {     // 0: two workgroup barriers per group, 1: LDS flags
+      return launch_lds<sweep_osr_kernel<double, TBSv, TBXv, NBR, 2, KIND, decltype(handoff)::value>>(pl->device, grid,
+          block, lds, st, fp, pl->D, pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(),
+          static_cast<const int4*>(sub ? pl->crow_s.p : pl->crow.p), cuts, pl->colscale.d(), rho, pl->KR, px, pp, sp.nsplit,
+          sp.ndt, static_cast<int*>(pl->flag.p) + 1);
+    };
+    return pl->os_barrier ? go(Int<0>{}) : go(Int<1>{});
+  });
+  return listed ? rc : fail(TEMX_EUNSUPPORTED, "single-sweep form: no instantiation for L = %d", pl->L);
 }
 
 template <int KIND>
@@ -1367,8 +1148,6 @@ static int os_tail(temx_plan* pl, const double* proj_s, int64_t t0, int64_t nts,
     TimedLaunch t2{};
     time_begin(pl, 1, st, t2);
     const size_t lds = os_contract_lds(pl->K, pl->KX, pl->NQ) * 8;
-    static std::atomic<uint64_t> attr_set{0};
-    if ((rc = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(os_contract_kernel<0>), 160 * 1024))) return rc;
     const double* Pp = pl->Ax.d() + (int64_t)4 * pl->KX * Dt;
     if (pl->osc_lds) {
       OsFields in;
@@ -1376,10 +1155,10 @@ static int os_tail(temx_plan* pl, const double* proj_s, int64_t t0, int64_t nts,
         in.A[f] = pl->Ax.d() + (int64_t)f * pl->KX * Dt;
         in.rho[f] = pl->rho.d() + (int64_t)f * pl->KR * pl->D;
       }
-      hipLaunchKernelGGL(os_contract_kernel<0>, dim3((unsigned)((Dt + OSC - 1) / OSC)), dim3(256), lds, st, in, Pp, pl->K, pl->KX,
-                         pl->KR, pl->NQ, Dt, pl->T.d(), pl->Ginv.d(), pl->G.d(), pl->Gx.d(), pl->gaunt.d(), pl->wq2.d(),
-                         pl->B4.d(), pl->B3.d(), pl->D, (int)nts, (int)pl->nt, (int)t0);
-      HIPCHK(hipGetLastError());
+      rc = launch_lds<os_contract_kernel<0>, 160 * 1024>(pl->device, dim3((unsigned)((Dt + OSC - 1) / OSC)), dim3(256), lds,
+          st, in, Pp, pl->K, pl->KX, pl->KR, pl->NQ, Dt, pl->T.d(), pl->Ginv.d(), pl->G.d(), pl->Gx.d(), pl->gaunt.d(),
+          pl->wq2.d(), pl->B4.d(), pl->B3.d(), pl->D, (int)nts, (int)pl->nt, (int)t0);
+      if (rc) return rc;
     } else {
       using KD = OsKind<0>;
       const int64_t QD = (int64_t)pl->NQ * Dt;
@@ -1475,8 +1254,6 @@ static int tracer_os_tail(temx_plan* pl, int nq, const double* projq_s, double* 
   if (pl->osc_lds) {
     if (nq != 1) return fail(TEMX_EUNSUPPORTED, "two tracers per sweep need the contraction on the matrix cores (TEMX_OPT_OS_CONTRACT = 0)");
     const size_t lds = os_contract_lds(pl->K, pl->KX, pl->NQ) * 8;
-    static std::atomic<uint64_t> attr_set{0};
-    if ((rc = lds_attr_once(attr_set, pl->device, reinterpret_cast<const void*>(os_contract_kernel<1>), 160 * 1024))) return rc;
     OsFields in{};
     in.A[0] = projq_s;
     in.A[1] = pl->Ax.d() + 1 * KXD;
@@ -1484,10 +1261,10 @@ static int tracer_os_tail(temx_plan* pl, int nq, const double* projq_s, double* 
     in.rho[0] = pl->rho_t.d();
     in.rho[1] = pl->rho.d() + 1 * KRD;
     in.rho[2] = pl->rho.d() + 3 * KRD;
-    hipLaunchKernelGGL(os_contract_kernel<1>, dim3((unsigned)((Dt + OSC - 1) / OSC)), dim3(256), lds, st, in, projq_s + KXD,
-                       pl->K, pl->KX, pl->KR, pl->NQ, Dt, pl->T.d(), pl->Ginv.d(), pl->G.d(), pl->Gx.d(), pl->gaunt.d(),
-                       pl->wq2.d(), Bq, Bq2, pl->D, (int)pl->tnt, (int)pl->nt, (int)pl->tt0);
-    HIPCHK(hipGetLastError());
+    rc = launch_lds<os_contract_kernel<1>, 160 * 1024>(pl->device, dim3((unsigned)((Dt + OSC - 1) / OSC)), dim3(256), lds,
+        st, in, projq_s + KXD, pl->K, pl->KX, pl->KR, pl->NQ, Dt, pl->T.d(), pl->Ginv.d(), pl->G.d(), pl->Gx.d(),
+        pl->gaunt.d(), pl->wq2.d(), Bq, Bq2, pl->D, (int)pl->tnt, (int)pl->nt, (int)pl->tt0);
+    if (rc) return rc;
   } else {
     // the q's are synthesised here; v and omega at the nodes are those the TEM tail left in the plan (osAt / osAb)
     const int64_t QD = (int64_t)pl->NQ * Dt;
@@ -1561,20 +1338,6 @@ static int bin_refuse(const char* what) {
               "serves temx_tem_run, temx_project and temx_zonal_mean", what);
 }
 
-#define TEMX_BIN_J(CALL)                                   \
-  switch (pl->bin_J) {                                     \
-    case 8: CALL(8); break;                                \
-    case 10: CALL(10); break;                              \
-    default: CALL(12); break;                              \
-  }
-#define TEMX_BIN_KP(CALL)                                  \
-  switch (pl->bin_KP) {                                    \
-    case 16: CALL(16); break;                              \
-    case 32: CALL(32); break;                              \
-    case 48: CALL(48); break;                              \
-    default: CALL(64); break;                              \
-  }
-
 static inline dim3 bin_sweep_grid(const temx_plan* pl, int64_t D) {
   const int Dw = (int)((D + 63) / 64);
   return dim3((unsigned)(pl->bin_nchunk * ((Dw + 3) / 4)));
@@ -1589,19 +1352,12 @@ static int launch_bin_moments(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype,
   const dim3 grid = bin_sweep_grid(pl, D);
   const int4* ch = static_cast<const int4*>(pl->bin_chunk.p);
   const int* rows = static_cast<const int*>(pl->bin_rows.p);
-#define TEMX_LBM(Jv)                                                                                                   \
-  do {                                                                                                                 \
-    if (dtype == TEMX_F64)                                                                                             \
-      hipLaunchKernelGGL((bin_moments_kernel<double, NF, Jv>), grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), \
-                         colscale, sfield, pl->bin_cm.d());                                                            \
-    else                                                                                                               \
-      hipLaunchKernelGGL((bin_moments_kernel<float, NF, Jv>), grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), \
-                         colscale, sfield, pl->bin_cm.d());                                                            \
-  } while (0)
-  TEMX_BIN_J(TEMX_LBM)
-#undef TEMX_LBM
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return by_dtype(dtype, [&](auto t) {
+    return dispatch(BinJValues{}, pl->bin_J, [&](auto j) {
+      return launch<bin_moments_kernel<typename decltype(t)::type, NF, decltype(j)::value>>(
+          grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), colscale, sfield, pl->bin_cm.d());
+    });
+  });
 }
 
 static inline double miss_thr(const temx_plan* pl) { return pl->opt_min_cov / 1000.0; }
@@ -1612,32 +1368,21 @@ static int miss_refuse(const char* what) {
 }
 
 // out[NF K + NE][D]: select-projections of the NF fields, then the projection of their common missing indicator
-template <typename T, int NF>
-static int launch_miss_project_t(temx_plan* pl, const FieldPtrs<NF>& fp, int64_t D, const double* colscale, int sfield,
-                                 double* out, hipStream_t st) {
-  const Split sp = choose_split(D, pl->nchunk, pl->num_cu, 4);
-  const int64_t R = (int64_t)NF * pl->K + pl->NE;
-  if (int rc = pl->partial.ensure(std::max((size_t)sp.nsplit * R * D * 8, pl->partial.bytes))) return rc;
-#define TEMX_LM(TBv)                                                                                              \
-  hipLaunchKernelGGL((miss_project_kernel<T, NF, TBv, 2 * TBv>), dim3(sp.grid), dim3(256), 0, st, fp, pl->N, D, pl->K, \
-                     pl->NE, pl->yblk.d(), pl->stride, pl->eblk.d(), pl->nchunk, colscale, sfield, pl->partial.d(),  \
-                     sp.nsplit, sp.ndt)
-  switch (pl->TB) {
-    case 4: TEMX_LM(4); break;
-    case 8: TEMX_LM(8); break;
-    case 13: TEMX_LM(13); break;
-    default: TEMX_LM(16); break;
-  }
-#undef TEMX_LM
-  HIPCHK(hipGetLastError());
-  return launch_reduce(pl, pl->partial.d(), sp.nsplit, R * D, out, st);
-}
 template <int NF>
 static int launch_miss_project(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int64_t D, const double* colscale,
                                int sfield, double* out, hipStream_t st) {
-  if (dtype == TEMX_F64) return launch_miss_project_t<double, NF>(pl, fp, D, colscale, sfield, out, st);
-  if (dtype == TEMX_F32) return launch_miss_project_t<float, NF>(pl, fp, D, colscale, sfield, out, st);
-  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  return by_dtype(dtype, [&](auto t) {
+    const Split sp = choose_split(D, pl->nchunk, pl->num_cu, 4);
+    const int64_t R = (int64_t)NF * pl->K + pl->NE;
+    if (int rc = pl->partial.ensure(std::max((size_t)sp.nsplit * R * D * 8, pl->partial.bytes))) return rc;
+    const int rc = dispatch(TBValues{}, pl->TB, [&](auto tb) {
+      constexpr int TBv = decltype(tb)::value;
+      return launch<miss_project_kernel<typename decltype(t)::type, NF, TBv, 2 * TBv>>(
+          dim3(sp.grid), dim3(256), 0, st, fp, pl->N, D, pl->K, pl->NE, pl->yblk.d(), pl->stride, pl->eblk.d(), pl->nchunk,
+          colscale, sfield, pl->partial.d(), sp.nsplit, sp.ndt);
+    });
+    return rc ? rc : launch_reduce(pl, pl->partial.d(), sp.nsplit, R * D, out, st);
+  });
 }
 
 template <int NR>
@@ -1661,40 +1406,30 @@ static int launch_miss_system(temx_plan* pl, const double* Bf, const double* E, 
 // the masked eddy sweep: products under the common mask, projected on Q (generic sweep on every grid)
 static int launch_miss_eddy(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, hipStream_t st) {
   EddyOut none{};
-  if (dtype == TEMX_F64) return launch_eddy_t<double, 0, 2>(pl, fp, pl->mC.d(), pl->partial.d(), pl->sp_eddy, none, st);
-  if (dtype == TEMX_F32) return launch_eddy_t<float, 0, 2>(pl, fp, pl->mC.d(), pl->partial.d(), pl->sp_eddy, none, st);
-  return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  return by_dtype(dtype, [&](auto t) {
+    return launch_eddy_t<typename decltype(t)::type, 0, 2>(pl, fp, pl->mC.d(), pl->partial.d(), pl->sp_eddy, none, st);
+  });
 }
 
 static int launch_miss_eddy_native(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, int64_t row0, int64_t nrows,
                                    const EddyOut& eo, hipStream_t st) {
   const int64_t n = nrows * pl->D;
   const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)pl->num_cu * 16));
-#define TEMX_LMN(T)                                                                                                   \
-  hipLaunchKernelGGL(miss_eddy_native_kernel<T>, grid, dim3(256), 0, st, fp, row0, nrows, pl->D, pl->K, pl->K4,        \
-                     pl->yblk.d(), pl->stride, pl->mC.d(), pl->mCcov.d(), pl->colscale.d(), miss_thr(pl), eo)
-  if (dtype == TEMX_F64) TEMX_LMN(double);
-  else if (dtype == TEMX_F32) TEMX_LMN(float);
-  else return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
-#undef TEMX_LMN
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return by_dtype(dtype, [&](auto t) {
+    return launch<miss_eddy_native_kernel<typename decltype(t)::type>>(grid, dim3(256), 0, st, fp, row0, nrows, pl->D,
+        pl->K, pl->K4, pl->yblk.d(), pl->stride, pl->mC.d(), pl->mCcov.d(), pl->colscale.d(), miss_thr(pl), eo);
+  });
 }
 
 static int launch_miss_native(temx_plan* pl, const void* A, int dtype, int64_t D, const double* C, const double* Ccov,
                               double* out, hipStream_t st) {
   const int64_t n = pl->N * D;
   const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)pl->num_cu * 16));
-  if (dtype == TEMX_F64)
-    hipLaunchKernelGGL(miss_native_kernel<double>, grid, dim3(256), 0, st, static_cast<const double*>(A), pl->N, D, pl->K,
-                       pl->yblk.d(), pl->stride, C, Ccov, miss_thr(pl), out);
-  else if (dtype == TEMX_F32)
-    hipLaunchKernelGGL(miss_native_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(A), pl->N, D, pl->K,
-                       pl->yblk.d(), pl->stride, C, Ccov, miss_thr(pl), out);
-  else
-    return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch<miss_native_kernel<T>>(grid, dim3(256), 0, st, static_cast<const T*>(A), pl->N, D, pl->K, pl->yblk.d(),
+        pl->stride, C, Ccov, miss_thr(pl), out);
+  });
 }
 
 // ---- vertical interpolation: launchers (kernels_vert.hpp, include/temx_vert.h) -----------------------------------
@@ -1835,31 +1570,25 @@ void temx_plan_destroy(temx_plan* pl) {
   delete pl;
 }
 
-// the basis kernels keep one row of K values per thread: 64 in registers, 512 (L <= 511) in scratch
-#define TEMX_BASIS(kern, K, ...)                          \
-  do {                                                    \
-    if ((K) <= 64)                                        \
-      hipLaunchKernelGGL(kern<64>, __VA_ARGS__);          \
-    else                                                  \
-      hipLaunchKernelGGL(kern<512>, __VA_ARGS__);         \
-  } while (0)
-
 // native rows: canonical [N][K] copy (Y0c, may be null) and the 4x4 blocks of the sweeps (yblk, may be null);
 // T: null for Y0 itself, or the device copy of R^-1 for the rows of Q = Y0 R^-1
 static int build_basis(temx_plan* pl, const double* rowscale_dev, const double* T, double* Y0c, double* yblk) {
   const int64_t npad = pl->nchunk * 16;
-  TEMX_BASIS(basis_kernel, pl->K, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, 0, pl->x.d(), pl->N, npad, pl->K,
-             pl->stride, pl->norm.d(), rowscale_dev, T, Y0c, yblk);
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return by_basis_rows(pl->K, [&](auto r) {
+    return launch<basis_kernel<decltype(r)::value>>(dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, nullptr, pl->x.d(),
+        pl->N, npad, pl->K, pl->stride, pl->norm.d(), rowscale_dev, T, Y0c, yblk);
+  });
 }
 
 // rows at the output latitudes: canonical [M][K] into `dst`; for K <= 64 also the blocked copy of Qp
 static int build_out_basis(temx_plan* pl, const double* T, double* dst, bool blocks) {
   const int64_t mch = (pl->M + 15) / 16;
-  TEMX_BASIS(basis_kernel, pl->K, dim3((unsigned)((mch * 16 + 255) / 256)), dim3(256), 0, 0, pl->xo.d(), (int64_t)pl->M,
-             mch * 16, pl->K, pl->stride, pl->norm.d(), (const double*)nullptr, T, dst, (double*)nullptr);
-  HIPCHK(hipGetLastError());
+  const int rc = by_basis_rows(pl->K, [&](auto r) {
+    return launch<basis_kernel<decltype(r)::value>>(dim3((unsigned)((mch * 16 + 255) / 256)), dim3(256), 0, nullptr,
+        pl->xo.d(), (int64_t)pl->M, mch * 16, pl->K, pl->stride, pl->norm.d(), (const double*)nullptr, T, dst,
+        (double*)nullptr);
+  });
+  if (rc) return rc;
   HIPCHK(hipDeviceSynchronize());
   if (blocks && pl->K <= 64) {   // blocked copy for solve_mfma_kernel
     std::vector<double> yp((size_t)pl->M * pl->K);
@@ -1872,25 +1601,29 @@ static int build_out_basis(temx_plan* pl, const double* T, double* dst, bool blo
 // basis rows at the class latitudes (kernels_cls.hpp): ycls, or the 64-harmonic slices ycls_l
 static int build_cls_basis(temx_plan* pl, const double* T) {
   const unsigned nb = (unsigned)((pl->cls_npad + 255) / 256);
-  if (pl->lcls) {
-    for (int sl = 0; sl < pl->nslice; ++sl)
-      TEMX_BASIS(cls_basis_slice_kernel, pl->K, dim3(nb), dim3(256), 0, 0, pl->xc.d(), pl->ncls, pl->cls_npad, pl->K,
-                 64 * sl, pl->norm.d(), T, pl->ycls_l.d() + sl * pl->ycls_lstride);
-  } else if (pl->cls) {
-    TEMX_BASIS(cls_basis_kernel, pl->K, dim3(nb), dim3(256), 0, 0, pl->xc.d(), pl->ncls, pl->cls_npad, pl->K, pl->TBS,
-               pl->norm.d(), T, pl->ycls.d());
-  }
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return by_basis_rows(pl->K, [&](auto r) {
+    constexpr int R = decltype(r)::value;
+    if (pl->lcls) {
+      for (int sl = 0; sl < pl->nslice; ++sl)
+        hipLaunchKernelGGL(cls_basis_slice_kernel<R>, dim3(nb), dim3(256), 0, 0, pl->xc.d(), pl->ncls, pl->cls_npad, pl->K,
+            64 * sl, pl->norm.d(), T, pl->ycls_l.d() + sl * pl->ycls_lstride);
+    } else if (pl->cls) {
+      hipLaunchKernelGGL(cls_basis_kernel<R>, dim3(nb), dim3(256), 0, 0, pl->xc.d(), pl->ncls, pl->cls_npad, pl->K, pl->TBS,
+                         pl->norm.d(), T, pl->ycls.d());
+    }
+    HIPCHK(hipGetLastError());
+    return (int)TEMX_OK;
+  });
 }
 
 static int build_sym_basis(temx_plan* pl, const double* T) {
   if (!pl->sym) return TEMX_OK;
   const int64_t n4 = pl->npg_alloc * 4;
-  TEMX_BASIS(sym_basis_kernel, pl->K, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, 0, pl->x.d(),
-             static_cast<const int*>(pl->rows.p), pl->npair, n4, pl->K, pl->TBS, pl->norm.d(), T, pl->ysym.d());
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return by_basis_rows(pl->K, [&](auto r) {
+    return launch<sym_basis_kernel<decltype(r)::value>>(dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, nullptr, pl->x.d(),
+                                                        static_cast<const int*>(pl->rows.p), pl->npair, n4, pl->K, pl->TBS,
+                                                        pl->norm.d(), T, pl->ysym.d());
+  });
 }
 
 // every projection / reconstruction operand of the plan in the basis T (null: Y0 itself)
@@ -2781,7 +2514,7 @@ static int launch_eddy_from_xbar(temx_plan* pl, const FieldPtrs<4>& fp, int dtyp
   else if (dtype == TEMX_F32)
     hipLaunchKernelGGL(eddy_from_xbar_kernel<float>, grid, block, 0, st, fp, xb, nrows, pl->D, colscale, eo);
   else
-    return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+    return bad_dtype();
   HIPCHK(hipGetLastError());
   return TEMX_OK;
 }
@@ -2955,7 +2688,7 @@ int temx_tem_os_prepass(temx_plan* pl, const void* ua, const void* va, const voi
   int rc = os_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !As) return fail(TEMX_EINVAL, "null argument");
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   HIPCHK(hipSetDevice(pl->device));
   return os_prepass(pl, four(ua, va, ta, wap), dtype, As, S_(stream));
 } TEMX_CATCH
@@ -2967,7 +2700,7 @@ int temx_tem_os_sweep(temx_plan* pl, const void* ua, const void* va, const void*
   int rc = os_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !As || !proj) return fail(TEMX_EINVAL, "null argument");
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   if ((rc = slices_ok(pl, nslices))) return rc;
   HIPCHK(hipSetDevice(pl->device));
   return os_sweep(pl, four(ua, va, ta, wap), dtype, As, nslices, proj, S_(stream));
@@ -2989,7 +2722,7 @@ int temx_tem_os_tail(temx_plan* pl, const double* proj_slice, int64_t t0, int64_
 static int tracers_args(const temx_plan* pl, int nq, const void* const* q_host, const void* va, const void* wap, int dtype) {
   if (nq != 1 && nq != 2) return fail(TEMX_EINVAL, "nq = %d: one or two tracers per sweep", nq);
   if (!q_host || !q_host[0] || (nq == 2 && !q_host[1]) || !va || !wap) return fail(TEMX_EINVAL, "null argument");
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   if (nq == 2 && (pl->os_tile || pl->osc_lds))
     return fail(TEMX_EUNSUPPORTED, "two tracers per sweep: not with TEMX_OPT_OS_MAP = tile / TEMX_OPT_OS_CONTRACT = lds");
   return TEMX_OK;
@@ -3110,7 +2843,7 @@ static int miss_setup(temx_plan* pl) {
 
 // temx_tem_run in missing-value mode: two reads of the four fields, per-d masked systems, the shared epilogue
 static int miss_tem_run(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double* results, double* zonal, hipStream_t st) {
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   int rc;
   if ((rc = miss_setup(pl))) return rc;
   const int64_t D = pl->D, KD = (int64_t)pl->K * D, MD = (int64_t)pl->M * D;
@@ -3148,7 +2881,7 @@ static int miss_tem_run(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double
 // temx_zonal_mean in missing-value mode (the field's own finiteness is the mask)
 static int miss_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* out, int native, hipStream_t st) {
   if (D < 1 || D >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "D must be in [1, 2^28)");
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   HIPCHK(hipSetDevice(pl->device));
   int rc;
   if ((rc = miss_setup(pl))) return rc;
@@ -3252,22 +2985,18 @@ static int bin_contract(temx_plan* pl, int NF, int64_t D, double* B, hipStream_t
   const int Dw = (int)((D + 63) / 64);
   const int* c0 = static_cast<const int*>(pl->bin_c0.p);
   const dim3 grid((unsigned)Dw, (unsigned)NF, BIN_SLABS);
-#define TEMX_LBC(KPv)                                                                                                  \
-  hipLaunchKernelGGL(bin_contract_kernel<KPv>, grid, dim3(64), 0, st, pl->bin_cm.d(), NF, pl->bin_J, D, Dw, pl->opt_lat_bins, \
-                     pl->K, c0, pl->bin_a.d(), pl->partial.d())
-  TEMX_BIN_KP(TEMX_LBC)
-#undef TEMX_LBC
-  HIPCHK(hipGetLastError());
-  int rc;
+  int rc = dispatch(BinKPValues{}, pl->bin_KP, [&](auto kp) {
+    return launch<bin_contract_kernel<decltype(kp)::value>>(grid, dim3(64), 0, st, pl->bin_cm.d(), NF, pl->bin_J, D, Dw,
+                                                            pl->opt_lat_bins, pl->K, c0, pl->bin_a.d(), pl->partial.d());
+  });
+  if (rc) return rc;
   if ((rc = launch_reduce(pl, pl->partial.d(), BIN_SLABS, (int64_t)NF * pl->K * D, B, st))) return rc;
   if (!pl->qbasis) return TEMX_OK;
   const dim3 gb((unsigned)Dw, (unsigned)NF);
-#define TEMX_LBB(KPv) \
-  hipLaunchKernelGGL(bin_basis_kernel<KPv>, gb, dim3(64), 0, st, B, (int64_t)pl->K, pl->bin_T.d(), pl->K, D, B, (int64_t)pl->K)
-  TEMX_BIN_KP(TEMX_LBB)
-#undef TEMX_LBB
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return dispatch(BinKPValues{}, pl->bin_KP, [&](auto kp) {
+    return launch<bin_basis_kernel<decltype(kp)::value>>(gb, dim3(64), 0, st, B, (int64_t)pl->K, pl->bin_T.d(), pl->K, D, B,
+                                                         (int64_t)pl->K);
+  });
 }
 
 // coefficients C[NF][K4][D] in the plan's basis -> the per-bin Chebyshev series z[B][NF][J][Dpad] of the native means
@@ -3276,22 +3005,19 @@ static int bin_synth(temx_plan* pl, int NF, int64_t D, const double* C, hipStrea
   const int* c0 = static_cast<const int*>(pl->bin_c0.p);
   const double* Tc = pl->bin_T.d() + (size_t)pl->bin_KP * pl->bin_KP;
   const dim3 gb((unsigned)Dw, (unsigned)NF), grid((unsigned)Dw, (unsigned)NF, BIN_SLABS);
-#define TEMX_LBS(KPv)                                                                                                  \
-  do {                                                                                                                 \
-    hipLaunchKernelGGL(bin_basis_kernel<KPv>, gb, dim3(64), 0, st, C, (int64_t)pl->K4, Tc, pl->K, D, pl->bin_cy.d(), (int64_t)pl->K); \
-    hipLaunchKernelGGL(bin_synth_kernel<KPv>, grid, dim3(64), 0, st, pl->bin_cy.d(), NF, pl->bin_J, D, Dw, pl->opt_lat_bins, \
-                       pl->K, c0, pl->bin_a.d(), pl->bin_z.d());                                                       \
-  } while (0)
-  TEMX_BIN_KP(TEMX_LBS)
-#undef TEMX_LBS
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return dispatch(BinKPValues{}, pl->bin_KP, [&](auto kp) {
+    constexpr int KP = decltype(kp)::value;
+    hipLaunchKernelGGL(bin_basis_kernel<KP>, gb, dim3(64), 0, st, C, (int64_t)pl->K4, Tc, pl->K, D, pl->bin_cy.d(),
+        (int64_t)pl->K);
+    return launch<bin_synth_kernel<KP>>(grid, dim3(64), 0, st, pl->bin_cy.d(), NF, pl->bin_J, D, Dw, pl->opt_lat_bins,
+        pl->K, c0, pl->bin_a.d(), pl->bin_z.d());
+  });
 }
 
 // temx_tem_run with latitude bins: two reads of the four fields; B4, C4, the zonal means and the validity flags are
 // left as the generic two-pass stages leave them, so that the eddies and the tracers run their own kernels afterwards
 static int bin_tem_run(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double* results, double* zonal, hipStream_t st) {
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   int rc;
   if ((rc = bin_setup(pl))) return rc;
   const int64_t D = pl->D;
@@ -3314,26 +3040,21 @@ static int bin_tem_run(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double*
   const int* rows = static_cast<const int*>(pl->bin_rows.p);
   TimedLaunch tl2{};
   time_begin(pl, 1, st, tl2);
-#define TEMX_LBE(Jv)                                                                                                   \
-  do {                                                                                                                 \
-    if (dtype == TEMX_F64)                                                                                             \
-      hipLaunchKernelGGL((bin_eddy_moments_kernel<double, Jv>), grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), \
-                         pl->colscale.d(), pl->bin_z.d(), pl->bin_cm.d());                                             \
-    else                                                                                                               \
-      hipLaunchKernelGGL((bin_eddy_moments_kernel<float, Jv>), grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), \
-                         pl->colscale.d(), pl->bin_z.d(), pl->bin_cm.d());                                             \
-  } while (0)
-  TEMX_BIN_J(TEMX_LBE)
-#undef TEMX_LBE
+  rc = by_dtype(dtype, [&](auto t) {
+    return dispatch(BinJValues{}, pl->bin_J, [&](auto j) {
+      return launch<bin_eddy_moments_kernel<typename decltype(t)::type, decltype(j)::value>>(
+          grid, dim3(256), 0, st, fp, D, Dw, ch, rows, pl->bin_s.d(), pl->colscale.d(), pl->bin_z.d(), pl->bin_cm.d());
+    });
+  });
   time_end(pl, 1, st, tl2);
-  HIPCHK(hipGetLastError());
+  if (rc) return rc;
   if ((rc = bin_contract(pl, 3, D, pl->B3.d(), st))) return rc;
   return tem_stage3_impl(pl, pl->B3.d(), results, zonal, st);
 }
 
 // temx_project with latitude bins
 static int bin_project_op(temx_plan* pl, const void* A, int dtype, int64_t D, double* B, hipStream_t st) {
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   int rc;
   if ((rc = bin_setup(pl))) return rc;
   if ((rc = bin_workspace(pl, D, 1))) return rc;
@@ -3358,12 +3079,10 @@ static int bin_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, do
   const int Dw = (int)((D + 63) / 64);
   const int4* ch = static_cast<const int4*>(pl->bin_chunk.p);
   const int* rows = static_cast<const int*>(pl->bin_rows.p);
-#define TEMX_LBN(Jv) \
-  hipLaunchKernelGGL(bin_native_kernel<Jv>, bin_sweep_grid(pl, D), dim3(256), 0, st, D, Dw, ch, rows, pl->bin_s.d(), pl->bin_z.d(), out)
-  TEMX_BIN_J(TEMX_LBN)
-#undef TEMX_LBN
-  HIPCHK(hipGetLastError());
-  return TEMX_OK;
+  return dispatch(BinJValues{}, pl->bin_J, [&](auto j) {
+    return launch<bin_native_kernel<decltype(j)::value>>(bin_sweep_grid(pl, D), dim3(256), 0, st, D, Dw, ch, rows,
+        pl->bin_s.d(), pl->bin_z.d(), out);
+  });
 }
 
 int temx_tem_run(temx_plan* pl, const void* ua, const void* va, const void* ta, const void* wap,
@@ -3383,7 +3102,7 @@ int temx_tem_run(temx_plan* pl, const void* ua, const void* va, const void* ta, 
   if (os_active(pl, dtype)) {
     if ((rc = os_ready(pl))) return rc;
     if (!ua || !va || !ta || !wap || !results) return fail(TEMX_EINVAL, "null argument");
-    if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+    if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
     HIPCHK(hipSetDevice(pl->device));
     return tem_run_os(pl, four(ua, va, ta, wap), dtype, results, zonal, stream);
   }
@@ -3425,7 +3144,7 @@ int temx_tem_eddy_rows(temx_plan* pl, const void* ua, const void* va, const void
   if (row0 < 0 || nrows < 1 || row0 + nrows > pl->N || (row0 & 15))
     return fail(TEMX_EINVAL, "row range [%lld, %lld) must lie inside the grid and start at a multiple of 16",
                 (long long)row0, (long long)(row0 + nrows));
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   HIPCHK(hipSetDevice(pl->device));
   if (!tail_is_whole(pl)) return fail(TEMX_ESTATE, "the plan holds the coefficients of a time slice (temx_tem_os_tail), not of the whole run");
   hipStream_t st = S_(stream);
@@ -3611,7 +3330,7 @@ int temx_tem_tracer_stage1(temx_plan* pl, const void* ua, const void* va, const 
   int rc = tem_ready(pl);
   if (rc) return rc;
   if (!ua || !va || !ta || !wap || !q || !B4 || !Bq) return fail(TEMX_EINVAL, "null argument");
-  if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
   if (!(pl->cls && pl->onepass) || pl->large)
     return fail(TEMX_ESTATE, "the fused TEM + tracer sweep needs the one-pass class path (temx_plan_one_pass)");
   HIPCHK(hipSetDevice(pl->device));
@@ -3670,7 +3389,7 @@ int temx_tracer_run(temx_plan* pl, const void* q, const void* va, const void* wa
   if (rc) return rc;
   if (pl->os_valid && pl->c4_valid && tail_is_whole(pl) && os_active(pl, dtype)) {   // after a single-sweep TEM run: the tracer's single sweep
     if (!q || !va || !wap || !tres) return fail(TEMX_EINVAL, "null argument");
-    if (dtype != TEMX_F64 && dtype != TEMX_F32) return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+    if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
     HIPCHK(hipSetDevice(pl->device));
     const void* qs[1] = {q};
     double* tr[1] = {tres};
@@ -3771,7 +3490,7 @@ int temx_synth_fields(int device, int64_t ncol, int nlev, int64_t nt, int64_t t0
     hipLaunchKernelGGL(synth_kernel<float>, grid, block, 0, S_(stream), ncol, nlev, nt, t0, lat_deg, lon_deg,
                        plev_hpa, seed, (float*)ua, (float*)va, (float*)ta, (float*)wap);
   } else {
-    return fail(TEMX_EINVAL, "dtype must be TEMX_F64 or TEMX_F32");
+    return bad_dtype();
   }
   HIPCHK(hipGetLastError());
   return TEMX_OK;

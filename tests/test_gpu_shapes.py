@@ -10,14 +10,15 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
-def run_case(ne, nlev, nt, L=50, dtype=np.float64, seed=0):
+def run_case(ne, nlev, nt, L=50, dtype=np.float64, seed=0, **plan_kw):
+    """The pipeline against the oracle; plan_kw goes to engine.Plan.  Returns the plan's sweep mode."""
     from oracle import tem_oracle as orc
     from pytemdiags_amd import _lib, engine, synth
     lat, lon = synth.cubed_sphere_gll(ne)
     plev = synth.pressure_levels(nlev)
     f = synth.analytic_fields(lat, lon, plev, nt, seed=seed, dtype=dtype)
     ref = orc.TEMOracle(*f, lat, plev, L=L, mode="factorised")
-    plan = engine.Plan(lat, ref.lat, L)
+    plan = engine.Plan(lat, ref.lat, L, **plan_kw)
     plan.set_tem(nlev, nt, plev * 100)
     dev = [torch.as_tensor(x, device="cuda:0") for x in f]
     res, zon = plan.tem_run(*dev, want_zonal=True)
@@ -30,7 +31,9 @@ def run_case(ne, nlev, nt, L=50, dtype=np.float64, seed=0):
     for i, n in enumerate(_lib.ZONAL_NAMES):
         e = fieldnorm_err(zon[i], getattr(ref, n))
         assert e <= tol, (ne, nlev, nt, n, e)
+    mode = plan.sweep_mode
     plan.close()
+    return mode
 
 
 @pytest.mark.parametrize("ne,nlev,nt,L", [
@@ -58,6 +61,26 @@ def test_pipeline_shapes_fp64(ne, nlev, nt, L):
 
 def test_pipeline_fp32_inputs():
     run_case(8, 30, 4, dtype=np.float32)
+
+
+SWEEP_MODES = [({}, 2), ({"classes": False}, 1), ({"symmetry": False}, 0)]       # latitude classes, mirror pairs, generic
+
+
+@pytest.mark.parametrize("nlev,nt,L,dtype,mode", [
+    # D = 21 (two d-tiles, ragged) at L = 15, 31, 50, 60: 4, 8, 13, 16 blocks of harmonics in the generic sweeps and
+    # 2, 4, 7, 8 per parity in the class and pair sweeps -- every entry of both lists, for both input types
+    *[(7, 3, L, dtype, mode) for L in (15, 31, 50, 60) for dtype in (np.float64, np.float32) for mode in range(3)],
+    # D = 72 and D = 128 at L = 50: one and four d-tiles per workgroup
+    *[(nlev, nt, 50, np.float64, mode) for nlev, nt in ((72, 1), (16, 8)) for mode in range(3)],
+])
+def test_every_listed_instantiation_in_every_sweep_mode(nlev, nt, L, dtype, mode):
+    """Each value a launcher turns into a template argument (csrc/dispatch.hpp), in the class, pair and generic sweeps,
+    against the oracle: a value routed to another instantiation reads the basis blocks with the wrong stride."""
+    import os
+    plan_kw, expected = SWEEP_MODES[mode]
+    got = run_case(8, nlev, nt, L, dtype, **plan_kw)
+    if os.environ.get("TEMX_NO_SYM") != "1" and os.environ.get("TEMX_NO_CLS") != "1":
+        assert got == expected
 
 
 def test_properties_at_baseline_grid_size():
