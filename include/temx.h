@@ -121,7 +121,7 @@ enum {
  *     every output.
  *   Entry points: temx_zonal_mean (native 0 and 1), temx_tem_run, temx_tem_eddy and temx_tem_eddy_rows run masked;
  *     temx_status reports 0 (non-finite input is data).  The staged, sharded and single-sweep entry points and every
- *     tracer entry point return TEMX_EUNSUPPORTED in this mode. */
+ *     tracer entry point return TEMX_EUNSUPPORTED in this mode.  Masked tracers: temx_mtracer.h (temxm_tracer_run). */
  /* Latitude-bin form (TEMX_OPT_LAT_BINS = B; opt-in, nothing selects it).
  *   For grids whose columns share no latitude (MPAS, ICON, a remapped file with noisy latitudes, any unstructured set),
  *     where the plan runs the generic sweeps: one row of K = L + 1 harmonics of matrix work per column.

@@ -571,6 +571,8 @@ constexpr int EDDY_GR = 2;   // groups (of 4 columns) per eddy step: 8 columns x
 // KIND 1: tracer   fields (q, v, omega);           products q'v', q'w'   (tem_diagnostics.py:532-538, 560-570)
 // KIND 2: TEM in missing-value mode (kernels_miss.hpp): as KIND 0 with per-d masked coefficients, and a product is
 //         projected as 0 where any of the four fields is not finite (a select: NaN * 0 is NaN); MODE 0 only
+// KIND 3: tracer in missing-value mode (kernels_mtracer.hpp): as KIND 1 with per-d masked coefficients, and a product
+//         is projected as 0 where any of q, v, omega is not finite (the same select); MODE 0 only
 template <typename T, int TB, int MODE, int DPW, int KIND>
 __global__ void __launch_bounds__(512, 2)
 eddy_kernel(FieldPtrs<4> fp, int64_t N, int64_t D, int K, const double* __restrict__ yblk,
@@ -591,8 +593,9 @@ eddy_kernel(FieldPtrs<4> fp, int64_t N, int64_t D, int K, const double* __restri
   constexpr int YE = GR * TB * 16;           // doubles of Y0 blocks per step
   constexpr int YJ = (YE + 63) / 64;         // staging loads per lane
   constexpr int NP = 8 / DPW;
-  constexpr int NFR = KIND == 1 ? 3 : 4;     // fields reconstructed
-  constexpr int NPR = KIND == 1 ? 2 : 3;     // products projected
+  constexpr bool TRACER = KIND == 1 || KIND == 3;
+  constexpr int NFR = TRACER ? 3 : 4;        // fields reconstructed
+  constexpr int NPR = TRACER ? 2 : 3;        // products projected
   int split, dq;
   if (!wg_work((ndt + DPW - 1) / DPW, nsplit, split, dq)) return;
   const int wave = uniform_wave(), lane = threadIdx.x & 63;
@@ -619,7 +622,7 @@ eddy_kernel(FieldPtrs<4> fp, int64_t N, int64_t D, int K, const double* __restri
   int cbi = w4 * (NFR * TB * 64) + lane;   // index of this lane's first slab element in lds[]
   double* yst = lds + DPW * NFR * TB * 64 + wave * YE;   // this wave's copy of the step's Y0 blocks
 
-  const double sth = (KIND != 1 && colscale != nullptr) ? colscale[dcl] : 1.0;
+  const double sth = (!TRACER && colscale != nullptr) ? colscale[dcl] : 1.0;
   const uint32_t loff = (uint32_t)(g * D + dcl);
   const uint32_t aoff_r = (uint32_t)((lane & 3) * 4 + g);   // reconstruction A[i -> column][k -> harmonic]
   const uint32_t aoff_p = (uint32_t)(g * 4 + (lane & 3));   // projection     A[i -> harmonic][k -> column]
@@ -668,7 +671,7 @@ eddy_kernel(FieldPtrs<4> fp, int64_t N, int64_t D, int K, const double* __restri
     for (int f = 0; f < NFR; ++f)
 #pragma unroll
       for (int ti = 0; ti < GR; ++ti) xs[f][ti] = (double)xn[f][ti];
-    if (KIND != 1) {
+    if (!TRACER) {
 #pragma unroll
       for (int ti = 0; ti < GR; ++ti) xs[2][ti] *= sth;
     }
@@ -705,7 +708,7 @@ eddy_kernel(FieldPtrs<4> fp, int64_t N, int64_t D, int K, const double* __restri
       double e[NFR];
 #pragma unroll
       for (int f = 0; f < NFR; ++f) e[f] = xs[f][ti] - rec[f][ti];
-      if (KIND != 1) {
+      if (!TRACER) {
         p[0][ti] = e[0] * e[1];                    // u'v'
         p[1][ti] = e[0] * e[NFR - 1];              // u'w'
         p[NPR - 1][ti] = e[1] * e[2];              // v'theta'
@@ -713,7 +716,7 @@ eddy_kernel(FieldPtrs<4> fp, int64_t N, int64_t D, int K, const double* __restri
         p[0][ti] = e[0] * e[1];                    // q'v'
         p[1][ti] = e[0] * e[2];                    // q'w'
       }
-      if (KIND == 2) {
+      if (KIND == 2 || KIND == 3) {
         bool ok = true;
 #pragma unroll
         for (int f = 0; f < NFR; ++f) ok = ok && isfinite(xs[f][ti]);
@@ -724,7 +727,7 @@ eddy_kernel(FieldPtrs<4> fp, int64_t N, int64_t D, int K, const double* __restri
         const int64_t row = ((int64_t)step * GR + ti) * 4 + g;
         if (dvalid && row < N) {
           const int64_t o = row * D + d;
-          if (KIND != 1) {
+          if (!TRACER) {
 #pragma unroll
             for (int f = 0; f < NFR; ++f)
               if (eo.p[f]) eo.p[f][o] = e[f];

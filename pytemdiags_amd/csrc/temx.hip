@@ -5,6 +5,7 @@
 #include "../../include/temx_layout.h"
 #include "../../include/temx_ingest.h"
 #include "../../include/temx_clim.h"
+#include "../../include/temx_mtracer.h"
 
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,7 @@
 #include "kernels_op2.hpp"
 #include "kernels_osc.hpp"
 #include "kernels_miss.hpp"
+#include "kernels_mtracer.hpp"
 #include "kernels_bin.hpp"
 #include "kernels_vert.hpp"
 #include "kernels_layout.hpp"
@@ -220,6 +222,10 @@ struct temx_plan {
   DevBuf mtab;                         // G2 [K][K], Zq [NQ][K], Yq [NQ][NE], Acov [K][K], c1 [K]
   DevBuf mB, mC, mCcov, mcov, mZ;      // sums [4K + NE][D], coefficients [4][K4][D], coverage coefficients [K4][D],
                                        // coverage [M][D], zonal scratch of the native operator [M][D]
+  // masked tracer run (kernels_mtracer.hpp, include/temx_mtracer.h): allocated at the first temxm_tracer_run
+  bool mt_valid = false;               // mtC / mtCcov hold the tracer of a temxm_tracer_run that followed the latest masked temx_tem_run
+  DevBuf mtB, mtB2, mtC, mtCcov, mtz;  // sums [K + NE][D] and [2 K][D], coefficients (q, v, omega) [3][K4][D], coverage
+                                       // coefficients of the tracer's mask [K4][D], qb qpvpb qpwappb [3][M][D]
   // latitude-bin form (kernels_bin.hpp, bin_tables.hpp; TEMX_OPT_LAT_BINS): nothing here is built or allocated before the
   // first binned temx_plan_set_tem / operator call
   int opt_lat_bins = 0;                // B in effect, 0 = off
@@ -499,7 +505,7 @@ static int launch_solve(temx_plan* pl, const double* B, int NF, int64_t D, doubl
 template <typename T, int MODE, int KIND>
 static int launch_eddy_t(temx_plan* pl, const FieldPtrs<4>& fp, const double* C, double* partial,
                          const Split& sp, const EddyOut& eo, hipStream_t st) {
-  constexpr int NFR = KIND == 1 ? 3 : 4;
+  constexpr int NFR = (KIND == 1 || KIND == 3) ? 3 : 4;
   return dispatch(DpwValues{}, sp.dpw, [&](auto dpw) {
     return dispatch(TBValues{}, pl->TB, [&](auto tb) {
       constexpr int DPW = decltype(dpw)::value, TBv = decltype(tb)::value;
@@ -1432,6 +1438,48 @@ static int launch_miss_native(temx_plan* pl, const void* A, int dtype, int64_t D
   });
 }
 
+// ---- masked tracer run: launchers (kernels_mtracer.hpp, include/temx_mtracer.h) ----------------------------------
+// chunks the rows of (q, v, omega) run ahead: 24 ring registers per chunk in fp64.  Two everywhere but at TB = 16 in
+// fp64, where 48 + 96 accumulator and 24 staging registers leave room for one inside the 256 of two waves per SIMD
+template <typename T, int TB>
+constexpr int mtracer_pd() { return (sizeof(T) == 8 && TB == 16) ? 1 : 2; }
+
+// out[K + NE][D]: the select-projection of q under the tracer's mask, then the projection of its missing indicator
+static int launch_miss_tracer_project(temx_plan* pl, const FieldPtrs<3>& fp, int dtype, double* out, hipStream_t st) {
+  const int64_t D = pl->D;
+  return by_dtype(dtype, [&](auto t) {
+    const Split sp = choose_split(D, pl->nchunk, 2 * pl->num_cu, 4);
+    const int64_t R = (int64_t)pl->K + pl->NE;
+    if (int rc = pl->partial.ensure(std::max((size_t)sp.nsplit * R * D * 8, pl->partial.bytes))) return rc;
+    const int rc = dispatch(TBValues{}, pl->TB, [&](auto tb) {
+      constexpr int TBv = decltype(tb)::value;
+      using T = typename decltype(t)::type;
+      return launch<miss_tracer_project_kernel<T, TBv, 2 * TBv, mtracer_pd<T, TBv>()>>(
+          dim3(sp.grid), dim3(256), 0, st, fp, pl->N, D, pl->K, pl->NE, pl->yblk.d(), pl->stride, pl->eblk.d(), pl->nchunk,
+          pl->partial.d(), sp.nsplit, sp.ndt);
+    });
+    return rc ? rc : launch_reduce(pl, pl->partial.d(), sp.nsplit, R * D, out, st);
+  });
+}
+
+// the masked tracer sweep: q'v', q'omega' under the tracer's mask, projected on Q (generic sweep on every grid)
+static int launch_miss_tracer_eddy(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, hipStream_t st) {
+  EddyOut none{};
+  return by_dtype(dtype, [&](auto t) {
+    return launch_eddy_t<typename decltype(t)::type, 0, 3>(pl, fp, pl->mtC.d(), pl->partial.d(), pl->sp_eddy, none, st);
+  });
+}
+
+static int launch_miss_tracer_native(temx_plan* pl, const FieldPtrs<3>& fp, int dtype, const TracerEddyOut& eo,
+                                     hipStream_t st) {
+  const int64_t n = pl->N * pl->D;
+  const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)pl->num_cu * 16));
+  return by_dtype(dtype, [&](auto t) {
+    return launch<miss_tracer_native_kernel<typename decltype(t)::type>>(grid, dim3(256), 0, st, fp, pl->N, pl->D, pl->K,
+        pl->K4, pl->yblk.d(), pl->stride, pl->mtC.d(), pl->mtCcov.d(), miss_thr(pl), eo);
+  });
+}
+
 // ---- vertical interpolation: launchers (kernels_vert.hpp, include/temx_vert.h) -----------------------------------
 // The tables of a call (hyam, hybm, pt, xt) live in device buffers that are never written again once uploaded, so
 // calls on any stream may share them: a call with a set seen before touches no allocator.
@@ -1559,6 +1607,7 @@ void temx_plan_destroy(temx_plan* pl) {
                     &pl->rho0, &pl->gaunt, &pl->wq2, &pl->Axq, &pl->rho_t, &pl->Gx, &pl->Gsinv, &pl->Ax, &pl->Axs, &pl->oscblk, &pl->osAt, &pl->osAb, &pl->osAtq, &pl->osAbq, &pl->Bqp})
     b->release();
   for (DevBuf* b : {&pl->eblk, &pl->mtab, &pl->mB, &pl->mC, &pl->mCcov, &pl->mcov, &pl->mZ}) b->release();
+  for (DevBuf* b : {&pl->mtB, &pl->mtB2, &pl->mtC, &pl->mtCcov, &pl->mtz}) b->release();
   for (DevBuf* b : {&pl->bin_a, &pl->bin_chunk, &pl->bin_c0, &pl->bin_rows, &pl->bin_s, &pl->bin_T, &pl->bin_cm, &pl->bin_z, &pl->bin_cy}) b->release();
   for (auto& kv : pl->csplits_s) kv.second.release();
   for (auto& kv : pl->csplits) kv.second.release();
@@ -2259,6 +2308,7 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
   pl->tem = false;
   pl->onepass = pl->lone = pl->op_valid = pl->xb_valid = pl->tq_valid = false;
   pl->os_on = pl->os_valid = false;
+  pl->miss_valid = pl->mt_valid = false;   // the masked coefficients describe the columns of the previous configuration
   pl->os_tile = tile_map(pl->opt_os_map, "TEMX_OS_MAP");
   {
     const char* e = getenv("TEMX_OS_CONTRACT");
@@ -2852,7 +2902,7 @@ static int miss_tem_run(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, double
   if ((rc = pl->mCcov.ensure((size_t)pl->K4 * D * 8))) return rc;
   if ((rc = pl->mcov.ensure((size_t)MD * 8))) return rc;
   set_tail(pl, 0, pl->nt);
-  pl->miss_valid = false;
+  pl->miss_valid = pl->mt_valid = false;
   pl->op_valid = pl->os_valid = pl->c4_valid = pl->tq_valid = pl->xb_valid = false;
   pl->miss_cov_D = -1;
   const double* E = pl->mB.d() + 4 * KD;
@@ -3731,6 +3781,78 @@ int temxc_tem_from_zonal_means(temx_plan* pl, double* zm8, int64_t nts, double* 
     return fail(TEMX_EUNSUPPORTED, "M * nlev * nts = %.0f is too large for one launch", (double)pl->M * pl->nlev * (double)nts);
   HIPCHK(hipSetDevice(pl->device));
   return tem_epilogue_on(pl, zm8, nts, results, zonal, S_(stream));
+} TEMX_CATCH
+
+// ---- tracer TEM in missing-value mode (include/temx_mtracer.h, kernels_mtracer.hpp) ----
+int temxm_version(void) { return 100; }
+
+// everything the two calls refuse, before any device call
+static int mtracer_ready(temx_plan* pl, const void* q, const void* va, const void* wap, const void* out, int dtype) {
+  if (!pl || !q || !va || !wap || !out) return fail(TEMX_EINVAL, "null argument");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
+  if (!miss_mode(pl))
+    return fail(TEMX_ESTATE, "the plan is not in missing-value mode (TEMX_OPT_MISSING = 1): temx_tracer_run serves it");
+  if (int rc = tem_ready(pl)) return rc;
+  if (!pl->miss_valid)
+    return fail(TEMX_ESTATE, "missing-value mode: the tracer needs a masked temx_tem_run on this plan first");
+  return TEMX_OK;
+}
+
+int temxm_tracer_run(temx_plan* pl, const void* q, const void* va, const void* wap, int dtype, double* tres,
+                     double* tzon, double* tcov, void* stream) try {
+  int rc = mtracer_ready(pl, q, va, wap, tres, dtype);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(pl->device));
+  const int64_t D = pl->D, KD = (int64_t)pl->K * D, MD = (int64_t)pl->M * D;
+  const size_t slab = (size_t)pl->K4 * D * 8;
+  if ((rc = pl->mtB.ensure((size_t)(KD + (int64_t)pl->NE * D) * 8))) return rc;
+  if ((rc = pl->mtB2.ensure((size_t)2 * KD * 8))) return rc;
+  if ((rc = pl->mtC.ensure(3 * slab))) return rc;
+  if ((rc = pl->mtCcov.ensure(slab))) return rc;
+  if ((rc = pl->mtz.ensure((size_t)3 * MD * 8))) return rc;
+  hipStream_t st = S_(stream);
+  pl->mt_valid = false;
+  FieldPtrs<3> f3;
+  f3.p[0] = q; f3.p[1] = va; f3.p[2] = wap;
+  const double* E = pl->mtB.d() + KD;
+  TimedLaunch tl{};
+  time_begin(pl, 0, st, tl);
+  rc = launch_miss_tracer_project(pl, f3, dtype, pl->mtB.d(), st);
+  time_end(pl, 0, st, tl);
+  if (rc) return rc;
+  // Ct = (C_q, C_v, C_omega): C_q and the tracer's coverage coefficients from its own systems, qb -> tz[0]; v and
+  // omega keep the masked coefficients of the TEM run
+  if ((rc = launch_miss_system<1>(pl, pl->mtB.d(), E, D, pl->mtC.d(), pl->mtCcov.d(), pl->mtz.d(), tcov, st))) return rc;
+  HIPCHK(hipMemcpyAsync((char*)pl->mtC.p + slab, (char*)pl->mC.p + slab, slab, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync((char*)pl->mtC.p + 2 * slab, (char*)pl->mC.p + 3 * slab, slab, hipMemcpyDeviceToDevice, st));
+  TimedLaunch tl2{};
+  time_begin(pl, 1, st, tl2);
+  rc = launch_miss_tracer_eddy(pl, four(q, va, wap, nullptr), dtype, st);
+  time_end(pl, 1, st, tl2);
+  if (rc) return rc;
+  const int slabs = pl->sp_eddy.nsplit * (8 / pl->sp_eddy.dpw);
+  if ((rc = launch_reduce(pl, pl->partial.d(), slabs, 2 * KD, pl->mtB2.d(), st))) return rc;
+  // qpvpb qpwappb -> tz[1..2] with the tracer's systems
+  if ((rc = launch_miss_system<2>(pl, pl->mtB2.d(), E, D, nullptr, nullptr, pl->mtz.d() + MD, nullptr, st))) return rc;
+  EpiTables tb{pl->p.d(), pl->pg.d(), pl->lg.d(), pl->coslat.d(), pl->fcor.d()};
+  hipLaunchKernelGGL(tracer_epilogue_kernel, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, pl->zb.d(),
+                     pl->mtz.d(), pl->M, pl->nlev, pl->nt, tb, pl->p0, tres, tzon);
+  HIPCHK(hipGetLastError());
+  pl->mt_valid = true;
+  return TEMX_OK;
+} TEMX_CATCH
+
+int temxm_tracer_eddy(temx_plan* pl, const void* q, const void* va, const void* wap, int dtype,
+                      double* const* ptrs3_host, void* stream) try {
+  int rc = mtracer_ready(pl, q, va, wap, ptrs3_host, dtype);
+  if (rc) return rc;
+  if (!pl->mt_valid)
+    return fail(TEMX_ESTATE, "missing-value mode: no temxm_tracer_run since the latest masked temx_tem_run on this plan");
+  HIPCHK(hipSetDevice(pl->device));
+  FieldPtrs<3> f3;
+  f3.p[0] = q; f3.p[1] = va; f3.p[2] = wap;
+  TracerEddyOut eo{{ptrs3_host[0], ptrs3_host[1], ptrs3_host[2]}};
+  return launch_miss_tracer_native(pl, f3, dtype, eo, S_(stream));
 } TEMX_CATCH
 
 }  // extern "C"

@@ -572,6 +572,33 @@ class Plan:
         check(self.lib.temx_tracer_eddy(self._h, _ptr(qq), _ptr(v), _ptr(w), dt, ptrs, self._stream()))
         return outs
 
+    # ---- tracer TEM in missing-value mode (include/temx_mtracer.h; needs a preceding masked tem_run) ----
+    def tracer_run_masked(self, q, va, wap, want_zonal=False):
+        """One tracer with a mask of its own (valid where ``q``, ``va`` and ``wap`` are all finite) on a plan in
+        missing-value mode, after ``tem_run`` on the same ``va``, ``wap`` (temxm_tracer_run).
+        -> (results ``[6][M][nlev][nt]``, zonal intermediates ``[6][M][nlev][nt]`` or None, the tracer's coverage
+        ``[M][nlev][nt]``)."""
+        from . import _mtracer
+        lib = _mtracer.load()
+        (qq, v, w), dt = self._three(q, va, wap)
+        tres, tzon = self._alloc_tracer(want_zonal)
+        tcov = torch.empty((self.M, self.nlev, self.nt), dtype=torch.float64, device=self.device)
+        check(lib.temxm_tracer_run(self._h, _ptr(qq), _ptr(v), _ptr(w), dt, _ptr(tres),
+                                   _ptr(tzon) if tzon is not None else None, _ptr(tcov), self._stream()))
+        return tres, tzon, tcov
+
+    def tracer_eddy_masked(self, q, va, wap):
+        """``qp qpvp qpwapp`` of the tracer of the latest ``tracer_run_masked`` (temxm_tracer_eddy): NaN where the
+        point is not valid for the tracer or its native coverage is below ``min_coverage``."""
+        from . import _mtracer
+        lib = _mtracer.load()
+        (qq, v, w), dt = self._three(q, va, wap)
+        outs = {n: torch.empty((self.N, self.nlev, self.nt), dtype=torch.float64, device=self.device)
+                for n in _lib.TRACER_EDDY_NAMES}
+        ptrs = (C.c_void_p * 3)(*[outs[n].data_ptr() for n in _lib.TRACER_EDDY_NAMES])
+        check(lib.temxm_tracer_eddy(self._h, _ptr(qq), _ptr(v), _ptr(w), dt, ptrs, self._stream()))
+        return outs
+
     # ---- time-mean TEM (include/temx_clim.h) ----
     def time_sum(self, fields, acc=None, accumulate=False):
         """Sum over the last (time) axis of up to eight contiguous device tensors ``[ncol][nlev][nt]``, fp64 or fp32

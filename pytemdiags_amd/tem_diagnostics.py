@@ -42,7 +42,7 @@ class TEMDiagnostics:
                  dim_names=DEFAULT_DIMS, grid_name=None, zm_grid_name=None, map_save_dest=None,
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
-                 lat_bins=None, climatology=False):
+                 lat_bins=None, climatology=False, tracer_mask=None):
         # ---- time-mean TEM (not in the reference; climatology.py): checked before anything touches the device ----
         self._want_climatology = clim.check_flag(climatology, missing)
         self._climatology = None
@@ -55,8 +55,7 @@ class TEMDiagnostics:
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (missing,))
         if not 0.0 <= float(min_coverage) <= 1.0:
             raise ValueError("min_coverage must lie in [0, 1], got %r" % (min_coverage,))
-        if missing == "mask" and q is not None:
-            self._refuse_masked_tracers()
+        self.tracer_mask = self._check_tracer_mask(tracer_mask, missing, q)
         self.missing = missing
         self.min_coverage = float(min_coverage)
         # ---- latitude-bin form (not in the reference; opt-in, include/temx.h): checked before anything touches the device
@@ -108,7 +107,7 @@ class TEMDiagnostics:
                 self._clim.add(self._dev_fields)
                 self._clim.run_stationary()
             plan.set_tem(self.NLEV, self.NT, self._p_np, float(self.p0))
-            self._res, self._zon, self._cov, self._tres, self._tzon = self._run_block(
+            self._res, self._zon, self._cov, self._tres, self._tzon, self._tcov = self._run_block(
                 plan, self._dev_fields, self._dev_q, self.NT)
         else:
             self._run_blocked(plan)
@@ -148,11 +147,13 @@ class TEMDiagnostics:
     def _run_block(self, plan, fields, qs, nt):
         """One engine run over ``nt`` snapshots in engine layout (``plan.set_tem`` has been called for them):
         the whole record in the default mode, one time block under ``time_block=``.
-        -> (results, zonal intermediates, coverage or None, tracer results, tracer zonal intermediates)."""
+        -> (results, zonal intermediates, coverage or None, tracer results, tracer zonal intermediates, tracer
+        coverages -- empty unless ``tracer_mask="own"``)."""
         # (class-sum forms: the first tracer, when there is one, shares the sweep of the fields, temx_tem_tracer_run;
         #  single sweep: the tracers follow the TEM run in pairs, temx_tracers_run)
         fused = None
-        if self.ntrac and not plan.single_sweep:
+        masked_q = self.ntrac and self.missing == "mask"     # tracer_mask="own": one masked run per tracer
+        if self.ntrac and not masked_q and not plan.single_sweep:
             res, zon, *fused = plan.tem_tracer_run(*fields, qs[0], want_zonal=True)
         else:
             res, zon = plan.tem_run(*fields, want_zonal=True)
@@ -164,8 +165,15 @@ class TEMDiagnostics:
             raise RuntimeError("Variable has nans! Spectral zonal averager cannot handle nans; "
                                "please replace or remove them")
         # ---- tracers (tem_diagnostics.py:532-538, 560-570, 602-611): one engine call each ----
-        tres_all, tzon_all = [], []
-        if self.ntrac and plan.single_sweep:
+        tres_all, tzon_all, tcov_all = [], [], []
+        if masked_q:
+            for i in range(self.ntrac):
+                tres, tzon, tcov = plan.tracer_run_masked(qs[i], fields[1], fields[3], want_zonal=True)
+                tres_all.append(tres)
+                tzon_all.append(tzon)
+                tcov_all.append(tcov)
+                self._last_tracer = i
+        elif self.ntrac and plan.single_sweep:
             # the list of tracers in one engine call: two per sweep, (q1, q2, v, omega) read once
             for tres, tzon in plan.tracers_run(qs, fields[1], fields[3], want_zonal=True):
                 tres_all.append(tres)
@@ -183,7 +191,7 @@ class TEMDiagnostics:
         if self.ntrac and plan.status():
             raise RuntimeError("Variable has nans! Spectral zonal averager cannot handle nans; "
                                "please replace or remove them")
-        return res, zon, cov, tres_all, tzon_all
+        return res, zon, cov, tres_all, tzon_all, tcov_all
 
     def _run_blocked(self, plan):
         """``time_block=``: every TEM step is independent per snapshot (the tail couples latitude and pressure only),
@@ -223,12 +231,12 @@ class TEMDiagnostics:
                     def whole(x):
                         return torch.empty(tuple(x.shape[:-1]) + (self.NT,), dtype=x.dtype, device=x.device)
                     big = (whole(out[0]), whole(out[1]), None if out[2] is None else whole(out[2]),
-                           [whole(x) for x in out[3]], [whole(x) for x in out[4]])
+                           [whole(x) for x in out[3]], [whole(x) for x in out[4]], [whole(x) for x in out[5]])
                 big[0][..., t0:t1] = out[0]
                 big[1][..., t0:t1] = out[1]
                 if out[2] is not None:
                     big[2][..., t0:t1] = out[2]
-                for dst, x in zip(big[3] + big[4], out[3] + out[4]):
+                for dst, x in zip(big[3] + big[4] + big[5], out[3] + out[4] + out[5]):
                     dst[..., t0:t1] = x
                 del out
         finally:
@@ -238,7 +246,7 @@ class TEMDiagnostics:
             self._block_source = None
         if self._clim is not None and self.time_block is not None:
             self._clim.run_stationary()     # after the last block: a blocked run serves no native outputs
-        self._res, self._zon, self._cov, self._tres, self._tzon = big
+        self._res, self._zon, self._cov, self._tres, self._tzon, self._tcov = big
         self._last_tracer = None
 
     def _refuse_native(self, what):
@@ -277,7 +285,8 @@ class TEMDiagnostics:
         runs on the result with ``plev=`` and everything in ``kw`` (``missing=``, ``min_coverage=``, ``L=`` ...):
         the object equals ``TEMDiagnostics(*interp_to_pressure([ua, va, ta, wap], plev, ...), lat_native, plev=...)``.
         Targets below the surface come out NaN: pass ``missing="mask"`` for those (the default raises, as the
-        reference does for NaN input).
+        reference does for NaN input), and ``tracer_mask="own"`` with it when there are tracers: each tracer is then
+        fitted under a mask of its own (valid where it, ``va`` and ``wap`` are finite; ``tracer_coverage``).
 
         Two orders of the axes are served, named by ``dims=`` for raw arrays and by ``.dims`` for labelled ones:
         ``(horz, vert, time)`` as above, and C-contiguous ``(time, vert, horz)`` with ``ps`` as ``(time, horz)`` --
@@ -292,8 +301,7 @@ class TEMDiagnostics:
         from . import vertical
         if kw.get("missing", "raise") not in ("raise", "mask"):
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (kw["missing"],))
-        if kw.get("missing", "raise") == "mask" and q is not None:
-            cls._refuse_masked_tracers()
+        cls._check_tracer_mask(kw.get("tracer_mask"), kw.get("missing", "raise"), q)
         cls._check_lat_bins(kw.get("lat_bins"), kw.get("missing", "raise"))
         clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"))
         qs = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
@@ -441,10 +449,19 @@ class TEMDiagnostics:
         return obj
 
     @staticmethod
-    def _refuse_masked_tracers():
-        raise NotImplementedError("missing='mask' does not support tracers (q=): a masked tracer would need a "
-                                  "mask of its own; fill or drop the tracer's missing values, or run it "
-                                  "separately with missing='raise'")
+    def _check_tracer_mask(tracer_mask, missing, q):
+        """``tracer_mask`` as given (ValueError for an unknown value, or for "own" without ``missing="mask"``);
+        tracers next to ``missing="mask"`` without it keep raising NotImplementedError.  Host logic only."""
+        if tracer_mask not in (None, "own"):
+            raise ValueError("tracer_mask must be None or 'own', got %r" % (tracer_mask,))
+        if tracer_mask == "own" and missing != "mask":
+            raise ValueError("tracer_mask='own' needs missing='mask': in the default mode a tracer has no mask")
+        if missing == "mask" and q is not None and tracer_mask is None:
+            raise NotImplementedError("missing='mask' does not support tracers (q=) unless tracer_mask='own' is given: "
+                                      "a masked tracer has a mask of its own (valid where q, va and wap are all "
+                                      "finite) and a coverage of its own (tracer_coverage); or fill or drop the "
+                                      "tracer's missing values, or run it separately with missing='raise'")
+        return tracer_mask
 
     # ------------------------------------------------------------------------------------------
     def _config_dims(self):
@@ -714,10 +731,13 @@ class TEMDiagnostics:
         for i in range(self.ntrac):
             if self._teddy[i] is None:
                 plan = self.ZM._plan
+                run, eddy = plan.tracer_run, plan.tracer_eddy
+                if self.missing == "mask":      # tracer_mask="own"
+                    run, eddy = plan.tracer_run_masked, plan.tracer_eddy_masked
                 if self._last_tracer != i:      # the plan holds the coefficients of one tracer at a time
-                    plan.tracer_run(self._dev_q[i], self._dev_fields[1], self._dev_fields[3])
+                    run(self._dev_q[i], self._dev_fields[1], self._dev_fields[3])
                     self._last_tracer = i
-                self._teddy[i] = plan.tracer_eddy(self._dev_q[i], self._dev_fields[1], self._dev_fields[3])
+                self._teddy[i] = eddy(self._dev_q[i], self._dev_fields[1], self._dev_fields[3])
             out.append(self._wrap(self._teddy[i][name], name, src(i), native=True))
         return out
 
@@ -778,6 +798,18 @@ class TEMDiagnostics:
         if self.ntrac == 0:
             raise RuntimeError("no tracers present (argument `q` not passed at object construction)")
         return self._wrap(self._tres[qi][_lib.TRACER_RESULT_NAMES.index(name)], name, "q%d" % qi)
+
+    def tracer_coverage(self, qi=None):
+        """``tracer_mask="own"``: the spectral zonal-mean valid fraction of tracer ``qi`` on the zonal grid -- valid
+        where ``q``, ``va`` and ``wap`` are all finite -- labelled like ``coverage`` (float64); the tracer's outputs
+        are NaN where it is below ``min_coverage``.  None in the default mode."""
+        if qi is None and self.ntrac > 1:
+            raise RuntimeError("qi must be passed to tracer_coverage() when len(q) > 1!")
+        if self.ntrac == 0:
+            raise RuntimeError("no tracers present (argument `q` not passed at object construction)")
+        if not self._tcov:
+            return None
+        return self._wrap(self._tcov[qi or 0], "tracer_coverage", "q%d" % (qi or 0), force64=True)
 
     def etfy(self, qi=None): return self._tracer_result("etfy", qi)               # noqa: E704
     def etfz(self, qi=None): return self._tracer_result("etfz", qi)               # noqa: E704
