@@ -20,8 +20,33 @@ Device work: the time sum of the four resident fields (``engine.Plan.time_sum``,
 run), one TEM run on the fp64 mean fields, and three epilogues on supplied zonal means
 (``engine.Plan.tem_from_zonal_means``); all on the plan of the ordinary run, which runs last and leaves the plan's
 state as an object built without ``climatology`` has it.
+
+Fields with missing values (``climatology=True, missing="mask", min_time_coverage=v``, ``0 < v <= 1``).  The mask of
+real pressure-level data varies in time (surface pressure moves), so the time mean needs a contract of its own.  With
+``need = max(1, ceil(v NT - 1e-9))``:
+
+  * time-mean fields   per (column, level), each of the four fields is the sum over the times valid under the common
+    mask of the four (as the masked TEM run defines it) divided by their count, and missing (NaN) where the count is
+    below ``need``.  Sums and counts come from ``engine.Plan.time_sum_valid(common=True)``, fused into the block loop;
+    they accumulate across blocks under ``time_block=``.  Division and thresholding are torch on ``[ncol][nlev]``.
+  * stationary fluxes  ``upvpb upwappb vptpb`` of one masked TEM run (``nt = 1``) on those fp64 mean fields, under the
+    object's ``min_coverage``; its zonal coverage is ``tem.climatology.stationary_coverage``.
+  * mean state and total fluxes   per (lat, level) of the zonal grid, the mean over the snapshots whose per-snapshot
+    masked zonal means are finite, NaN where fewer than ``need`` are.  The seven zonal means share their NaN pattern,
+    so this is one ``time_sum_valid(common=False)`` call on the seven viewed as ``[7 M nlev rows][NT]``; the valid
+    fraction is ``tem.climatology.time_coverage``, shape ``(lat, plev, 1)``.
+  * transient fluxes   total - stationary.  Under a mask that varies in time this is a DEFINITION, not the identity it
+    is without missing values: the mean state averages per-snapshot masked fits over the snapshots that have one, the
+    stationary run fits the time-mean fields once, and the two no longer commute.
+  * the three sets share the mean state; each is the epilogue of that state and its fluxes, and NaN propagates through
+    the epilogue as it does in a masked run.
+
+The ordinary masked run goes last: per-snapshot results, ``coverage``, native attributes and the plan's state are bit
+for bit those of the same object built without ``climatology``.  No tracers, no ``lat_bins``, no grouped means.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
@@ -46,14 +71,33 @@ _NAN_MESSAGE = ("Variable has nans! Spectral zonal averager cannot handle nans; 
                 "please replace or remove them")
 
 
-def check_flag(climatology, missing):
-    """``climatology`` as a bool; ValueError for anything else and next to ``missing="mask"`` (no device needed)."""
+def check_flag(climatology, missing, min_time_coverage=None):
+    """``climatology`` as a bool; ValueError for anything else, next to ``missing="mask"`` unless ``min_time_coverage``
+    opts into the masked contract, and for a ``min_time_coverage`` without both or outside (0, 1] (no device needed)."""
     if not isinstance(climatology, (bool, np.bool_)):
         raise ValueError("climatology must be True or False, got %r" % (climatology,))
-    if climatology and missing == "mask":
+    if min_time_coverage is not None:
+        if not (climatology and missing == "mask"):
+            raise ValueError("min_time_coverage belongs to the masked climatology: it needs climatology=True and "
+                             "missing='mask'")
+        time_coverage_value(min_time_coverage)
+    elif climatology and missing == "mask":
         raise ValueError("climatology=True and missing='mask' exclude each other: a time mean over a mask that varies "
                          "in time needs a contract of its own")
     return bool(climatology)
+
+
+def time_coverage_value(min_time_coverage):
+    """``min_time_coverage`` as a float in (0, 1]; ValueError for anything else."""
+    v = min_time_coverage
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 < float(v) <= 1.0:
+        raise ValueError("min_time_coverage must be a number in (0, 1], got %r" % (v,))
+    return float(v)
+
+
+def times_needed(min_time_coverage, nt):
+    """``need = max(1, ceil(v NT - 1e-9))``: the valid times a point of the masked climatology needs."""
+    return max(1, int(math.ceil(float(min_time_coverage) * int(nt) - 1e-9)))
 
 
 def mean_time(time):
@@ -96,15 +140,26 @@ del _n
 
 class TEMClimatology:
     """``tem.climatology``: the three result sets of the time-mean TEM (module docstring).  ``nt`` is the number of
-    snapshots averaged, ``time`` the mean of their time coordinate, ``time_sum_path`` ``"kernel"`` or ``"torch"``."""
+    snapshots averaged, ``time`` the mean of their time coordinate, ``time_sum_path`` ``"kernel"`` or ``"torch"``.
+    Masked climatology: ``time_coverage`` is the fraction of the snapshots whose masked zonal means are finite and
+    ``stationary_coverage`` the zonal coverage of the run on the time-mean fields, both ``(lat, plev, 1)`` float64 and
+    labelled like ``ub``; None otherwise."""
 
-    def __init__(self, owner, sets, nt, time, time_sum_path):
+    def __init__(self, owner, sets, nt, time, time_sum_path, time_coverage=None, stationary_coverage=None):
         self.nt = int(nt)
         self.time = time
         self.time_sum_path = time_sum_path
+        self._owner, self._tcov, self._scov = owner, time_coverage, stationary_coverage
         for name in SET_NAMES:
             res, zon = sets[name]
             setattr(self, name, ResultSet(owner, name, res, zon, time))
+
+
+    def _coverage(self, t, name):
+        return None if t is None else self._owner._wrap(t, name, "ua", force64=True, time=self.time)
+
+    time_coverage = property(lambda s: s._coverage(s._tcov, "time_coverage"))
+    stationary_coverage = property(lambda s: s._coverage(s._scov, "stationary_coverage"))
 
 
 class Builder:
@@ -156,3 +211,57 @@ class Builder:
             zm7[4:7] = fluxes[name]
             sets[name] = self.plan.tem_from_zonal_means(zm7, want_zonal=True)
         return TEMClimatology(self.owner, sets, self.nt, mean_time(self.owner.time), self.path)
+
+
+class MaskedBuilder(Builder):
+    """The builder of a masked climatology (module docstring): the sums over valid times with their counts instead of
+    the plain time sums, a masked stationary run, counted and thresholded means on the zonal grid."""
+
+    def __init__(self, owner, plan, min_time_coverage):
+        super().__init__(owner, plan)
+        self.path = "kernel"
+        self.v = time_coverage_value(min_time_coverage)
+        self.cnt = None
+        self.stat_cov = None
+
+    def add(self, fields):
+        fields = list(fields)
+        first = self.acc is None
+        self.acc, self.cnt = self.plan.time_sum_valid(fields, acc=self.acc, cnt=self.cnt, accumulate=not first, common=True)
+        self.nt += int(fields[0].shape[-1])
+
+    @staticmethod
+    def _mean(acc, cnt, need):
+        import torch
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=acc.device)
+        return torch.where(cnt >= need, acc / cnt, nan)
+
+    def run_stationary(self):
+        o, plan = self.owner, self.plan
+        need = times_needed(self.v, self.nt)
+        means = [self._mean(a, self.cnt, need).unsqueeze(-1).contiguous() for a in self.acc]
+        self.acc = self.cnt = None
+        plan.set_tem(o.NLEV, 1, o._p_np, float(o.p0))
+        _, zon = plan.tem_run(*means, want_zonal=True)
+        self.stat_cov = plan.coverage().reshape(o.ZM_N, o.NLEV, 1)
+        if plan.status():
+            raise RuntimeError(_NAN_MESSAGE)
+        i0 = _lib.ZONAL_NAMES.index(FLUX_NAMES[0])
+        self.stat_flux = zon[i0:i0 + 3].clone()
+
+    def finish(self, zon_all):
+        """``zon_all``: ``[16][M][nlev][NT]`` of the ordinary masked run -> TEMClimatology."""
+        _, M, nlev, nt = zon_all.shape
+        need = times_needed(self.v, nt)
+        (acc,), (cnt,) = self.plan.time_sum_valid([zon_all[:7].reshape(7 * M * nlev, 1, nt)], common=False)
+        total = self._mean(acc, cnt, need).reshape(7, M, nlev, 1)
+        import torch
+        # (tensor by tensor: a true division, so that 3 of 5 is 0.6 and not 3 * 0.2)
+        tcov = torch.true_divide(cnt.reshape(7, M, nlev, 1)[0], torch.full((), float(nt), dtype=torch.float64, device=cnt.device))
+        fluxes = {"total": total[4:7], "stationary": self.stat_flux, "transient": total[4:7] - self.stat_flux}
+        sets = {}
+        for name in SET_NAMES:
+            zm7 = total.clone()
+            zm7[4:7] = fluxes[name]
+            sets[name] = self.plan.tem_from_zonal_means(zm7, want_zonal=True)
+        return TEMClimatology(self.owner, sets, self.nt, mean_time(self.owner.time), self.path, tcov, self.stat_cov)

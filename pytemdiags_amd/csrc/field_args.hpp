@@ -1,5 +1,5 @@
 // field_args.hpp -- host: the argument rules of the plan-free entry points (temxv_interp, temxl_to_engine,
-// temxi_records_to_pressure, temxc_time_sum), written once, and the level tables two of them share.  No HIP.
+// temxi_records_to_pressure, temxc_time_sum, temxn_time_sum_valid), written once, and the level tables two of them share.  No HIP.
 // A check returns a Refusal, which is true when the call is refused; the entry point hands its code and message to
 // fail().  Every refusal here is TEMX_EINVAL.  tests/host/field_args_main.cpp runs this header under the sanitizers.
 #ifndef TEMX_FIELD_ARGS_HPP
@@ -123,6 +123,28 @@ inline Refusal check_fields(const FieldSet& a) {
         return refuse("%s %d overlaps %s %d", a.out_name, f, a.out_name, g);
     }
   }
+  return {};
+}
+
+// temxn_time_sum_valid: nf inputs of one dtype, nf fp64 accumulators and ncnt fp64 counts (nf, or 1 under a common mask),
+// outputs of out_elems elements each.  The accumulators go by check_fields; a count obeys the rules of an accumulator
+// and overlaps no accumulator either.
+inline Refusal check_sum_valid(int nf, const void* const* src, int dtype, size_t src_elems, double* const* acc,
+                               double* const* cnt, int ncnt, size_t out_elems) {
+  int dts[16];
+  for (int f = 0; f < nf && f < 16; ++f) dts[f] = dtype;
+  if (Refusal r = check_fields({nf, src, dts, src_elems, (void* const*)acc, "acc", TEMX_F64, out_elems})) return r;
+  const size_t out_bytes = out_elems * sizeof(double);
+  for (int f = 0; f < ncnt; ++f) {
+    if (!cnt[f]) return refuse("cnt %d is null", f);
+    if ((uintptr_t)cnt[f] % sizeof(double)) return refuse("cnt %d is not aligned to its element size", f);
+  }
+  for (int f = 0; f < ncnt; ++f)
+    for (int g = 0; g < nf; ++g) {
+      if (extents_overlap(cnt[f], out_bytes, src[g], src_elems * dtype_size(dtype))) return refuse("cnt %d overlaps src %d", f, g);
+      if (extents_overlap(cnt[f], out_bytes, acc[g], out_bytes)) return refuse("cnt %d overlaps acc %d", f, g);
+      if (g < f && extents_overlap(cnt[f], out_bytes, cnt[g], out_bytes)) return refuse("cnt %d overlaps cnt %d", f, g);
+    }
   return {};
 }
 

@@ -6,6 +6,7 @@
 #include "../../include/temx_ingest.h"
 #include "../../include/temx_clim.h"
 #include "../../include/temx_mtracer.h"
+#include "../../include/temx_nclim.h"
 
 #include <hip/hip_runtime.h>
 
@@ -37,10 +38,12 @@
 #include "kernels_layout.hpp"
 #include "kernels_ingest.hpp"
 #include "kernels_clim.hpp"
+#include "kernels_nclim.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
 #include "bin_tables.hpp"
 #include "class_tables.hpp"
 #include "clim_shapes.hpp"
+#include "nclim_shapes.hpp"
 #include "dispatch.hpp"
 #include "field_args.hpp"
 #include "host_math.hpp"
@@ -1569,6 +1572,33 @@ static int launch_time_sum(const ClimPtrs& fp, int nf, int64_t rows, int64_t nt,
   }
   HIPCHK(hipGetLastError());
   return TEMX_OK;
+}
+
+// ---- the time sum over valid times (include/temx_nclim.h): NFT fields per workgroup, 1 in own-mask mode ----
+template <typename T, int NFT>
+static int launch_time_sum_valid(const NclimPtrs& fp, int nf, int64_t rows, int64_t nt, int accumulate, hipStream_t st) {
+  const NclimShape sh = nclim_shape(rows, nt, sizeof(T), NFT == 1 ? 1 : nf);
+  if (sh.nblk >= (int64_t(1) << 32) / NCLIM_THREADS)   // HIP takes fewer than 2^32 threads per grid dimension
+    return fail(TEMX_EUNSUPPORTED, "too many rows for one launch (%lld workgroups): sum the fields in parts", (long long)sh.nblk);
+  const dim3 grid((unsigned)sh.nblk, NFT == 1 ? (unsigned)nf : 1u);
+  if (sh.staged) {
+    if ((size_t)(NFT == 1 ? 1 : nf) * sh.rpb * sh.stride * sizeof(T) > (size_t)NCLIM_LDS_BYTES || sh.stride < nt)
+      return fail(TEMX_EINTERNAL, "staged rows of the time sum over valid times exceed their LDS budget");
+    hipLaunchKernelGGL((time_sum_valid_staged_kernel<T, NFT>), grid, dim3(NCLIM_THREADS), 0, st, fp, nf, rows, (int)nt, sh,
+                       accumulate);
+  } else {
+    hipLaunchKernelGGL((time_sum_valid_long_kernel<T, NFT>), grid, dim3(NCLIM_THREADS), 0, st, fp, nf, rows, nt, accumulate);
+  }
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+template <typename T>
+static int launch_time_sum_valid_nf(const NclimPtrs& fp, int nf, bool common, int64_t rows, int64_t nt, int accumulate,
+                                    hipStream_t st) {
+  if (!common) return launch_time_sum_valid<T, 1>(fp, nf, rows, nt, accumulate, st);
+  if (nf <= 4) return launch_time_sum_valid<T, 4>(fp, nf, rows, nt, accumulate, st);
+  return launch_time_sum_valid<T, NCLIM_NFMAX>(fp, nf, rows, nt, accumulate, st);
 }
 
 extern "C" {
@@ -3781,6 +3811,25 @@ int temxc_tem_from_zonal_means(temx_plan* pl, double* zm8, int64_t nts, double* 
     return fail(TEMX_EUNSUPPORTED, "M * nlev * nts = %.0f is too large for one launch", (double)pl->M * pl->nlev * (double)nts);
   HIPCHK(hipSetDevice(pl->device));
   return tem_epilogue_on(pl, zm8, nts, results, zonal, S_(stream));
+} TEMX_CATCH
+
+// ---- time-mean TEM in missing-value mode: the sum over the valid times (include/temx_nclim.h, kernels_nclim.hpp) ----
+int temxn_version(void) { return 100; }
+
+int temxn_time_sum_valid(int device, int nf, const void* const* src_host, int src_dtype, double* const* acc_host,
+                         double* const* cnt_host, int64_t ncol, int nlev, int64_t nt, int flags, void* stream) try {
+  ARGCHK(check_nf(nf, TEMXN_NF_MAX) | check_null(src_host, "src_host") | check_null(acc_host, "acc_host") |
+         check_null(cnt_host, "cnt_host") | check_dtype(src_dtype, "src_dtype") | check_sizes(ncol, nlev, nt, "nt") |
+         check_flags(flags, TEMXN_ACCUMULATE | TEMXN_COMMON_MASK));
+  const int64_t rows = ncol * nlev;
+  const bool common = (flags & TEMXN_COMMON_MASK) != 0;
+  ARGCHK(check_sum_valid(nf, src_host, src_dtype, (size_t)rows * nt, acc_host, cnt_host, common ? 1 : nf, (size_t)rows));
+  NclimPtrs fp{};
+  for (int f = 0; f < nf; ++f) fp.src[f] = src_host[f], fp.acc[f] = acc_host[f], fp.cnt[f] = cnt_host[common ? 0 : f];
+  HIPCHK(hipSetDevice(device));
+  const int accumulate = (flags & TEMXN_ACCUMULATE) ? 1 : 0;
+  if (src_dtype == TEMX_F64) return launch_time_sum_valid_nf<double>(fp, nf, common, rows, nt, accumulate, S_(stream));
+  return launch_time_sum_valid_nf<float>(fp, nf, common, rows, nt, accumulate, S_(stream));
 } TEMX_CATCH
 
 // ---- tracer TEM in missing-value mode (include/temx_mtracer.h, kernels_mtracer.hpp) ----

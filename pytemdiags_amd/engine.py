@@ -642,6 +642,59 @@ class Plan:
                                  _clim.ACCUMULATE if accumulate else 0, self._stream()))
         return acc
 
+    # ---- time-mean TEM in missing-value mode (include/temx_nclim.h) ----
+    def time_sum_valid(self, fields, acc=None, cnt=None, accumulate=False, common=True):
+        """Sum over the valid (finite) times of up to eight contiguous device tensors ``[ncol][nlev][nt]`` of one dtype,
+        fp64 or fp32, and the number of valid times (temxn_time_sum_valid).  ``common=True``: a time of a row is valid
+        iff it is finite in every field, and the fields share one count.  -> (a list of fp64 ``[ncol][nlev]`` sums, the
+        counts: one fp64 ``[ncol][nlev]`` tensor under ``common``, else a list of them); ``acc`` / ``cnt`` themselves
+        when given (``+=`` under ``accumulate``, which needs both)."""
+        from . import _nclim
+        lib = _nclim.load()
+        fields = list(fields)
+        if not 1 <= len(fields) <= _nclim.NF_MAX:
+            raise ValueError("time_sum_valid takes 1..%d fields, got %d" % (_nclim.NF_MAX, len(fields)))
+        shape = tuple(fields[0].shape)
+        if len(shape) != 3:
+            raise ValueError("fields must be [ncol][nlev][nt], got %d dims" % len(shape))
+        fs = []
+        for x in fields:
+            if not isinstance(x, torch.Tensor):
+                raise TypeError("device tensors expected")
+            if x.device != self.device:
+                raise ValueError("tensor on %s, plan on %s" % (x.device, self.device))
+            if x.dtype not in _DT:
+                raise TypeError("dtype must be float64 or float32, got %s" % x.dtype)
+            if x.dtype != fields[0].dtype:
+                raise TypeError("the fields of one call share a dtype, got %s and %s" % (fields[0].dtype, x.dtype))
+            if tuple(x.shape) != shape:
+                raise ValueError("field has shape %s, expected %s" % (tuple(x.shape), shape))
+            fs.append(x.contiguous())
+        n = len(fs)
+        if accumulate and (acc is None or cnt is None):
+            raise ValueError("accumulate=True needs acc= and cnt=")
+
+        def outputs(given, count, what):
+            if given is None:
+                return list(torch.empty((count,) + shape[:2], dtype=torch.float64, device=self.device).unbind(0))
+            given = [given] if isinstance(given, torch.Tensor) else list(given)
+            if len(given) != count:
+                raise ValueError("%s has %d tensors, expected %d" % (what, len(given), count))
+            for a in given:
+                if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float64
+                        and tuple(a.shape) == shape[:2] and a.is_contiguous()):
+                    raise ValueError("%s must hold contiguous float64 [ncol][nlev] tensors on the plan's device" % what)
+            return given
+        acc = outputs(acc, n, "acc")
+        cnt = outputs(cnt, 1 if common else n, "cnt")
+        src = (C.c_void_p * n)(*[x.data_ptr() for x in fs])
+        dst = (C.c_void_p * n)(*[a.data_ptr() for a in acc])
+        cdst = (C.c_void_p * n)(*([c.data_ptr() for c in cnt] + [None] * (n - len(cnt))))
+        flags = (_nclim.ACCUMULATE if accumulate else 0) | (_nclim.COMMON_MASK if common else 0)
+        check(lib.temxn_time_sum_valid(self.device_index, n, src, _DT[fs[0].dtype], dst, cdst, shape[0], shape[1], shape[2],
+                                       flags, self._stream()))
+        return acc, (cnt[0] if common else cnt)
+
     def tem_from_zonal_means(self, zm7, want_zonal=False):
         """The epilogue of a TEM run on zonal means the caller supplies (temxc_tem_from_zonal_means): ``zm7`` is
         ``[7][M][nlev][nts]`` fp64 in the order ``ub vb thetab wapb upvpb upwappb vptpb``, ``nts`` any value >= 1.

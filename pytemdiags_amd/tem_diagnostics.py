@@ -42,9 +42,10 @@ class TEMDiagnostics:
                  dim_names=DEFAULT_DIMS, grid_name=None, zm_grid_name=None, map_save_dest=None,
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
-                 lat_bins=None, climatology=False, tracer_mask=None):
+                 lat_bins=None, climatology=False, tracer_mask=None, min_time_coverage=None):
         # ---- time-mean TEM (not in the reference; climatology.py): checked before anything touches the device ----
-        self._want_climatology = clim.check_flag(climatology, missing)
+        self._want_climatology = clim.check_flag(climatology, missing, min_time_coverage)
+        self.min_time_coverage = None if min_time_coverage is None else clim.time_coverage_value(min_time_coverage)
         self._climatology = None
         # ---- blocked run over the time axis (not in the reference): checked before anything touches the device ----
         self.time_block = layout.check_time_block(time_block)
@@ -101,7 +102,10 @@ class TEMDiagnostics:
         self._last_tracer = None
         self._after_launch = None
         self.block_timing = None
-        self._clim = clim.Builder(self, plan) if self._want_climatology else None
+        self._clim = None
+        if self._want_climatology:
+            self._clim = (clim.Builder(self, plan) if self.min_time_coverage is None
+                          else clim.MaskedBuilder(self, plan, self.min_time_coverage))
         if self.time_block is None and self._block_source is None:
             if self._clim is not None:      # time means and their TEM first: the ordinary run is the plan's last
                 self._clim.add(self._dev_fields)
@@ -287,6 +291,9 @@ class TEMDiagnostics:
         Targets below the surface come out NaN: pass ``missing="mask"`` for those (the default raises, as the
         reference does for NaN input), and ``tracer_mask="own"`` with it when there are tracers: each tracer is then
         fitted under a mask of its own (valid where it, ``va`` and ``wap`` are finite; ``tracer_coverage``).
+        ``climatology=True`` next to ``missing="mask"`` needs ``min_time_coverage=v`` (``0 < v <= 1``): the time-mean
+        TEM over a mask that varies in time, a point kept where at least that fraction of the record is valid
+        (``climatology.py``).
 
         Two orders of the axes are served, named by ``dims=`` for raw arrays and by ``.dims`` for labelled ones:
         ``(horz, vert, time)`` as above, and C-contiguous ``(time, vert, horz)`` with ``ps`` as ``(time, horz)`` --
@@ -303,7 +310,7 @@ class TEMDiagnostics:
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (kw["missing"],))
         cls._check_tracer_mask(kw.get("tracer_mask"), kw.get("missing", "raise"), q)
         cls._check_lat_bins(kw.get("lat_bins"), kw.get("missing", "raise"))
-        clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"))
+        clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"), kw.get("min_time_coverage"))
         qs = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
         given = [ua, va, ta, wap] + qs
         if cls._model_level_order(given, kw.pop("dims", None), kw.get("dim_names", DEFAULT_DIMS)) == "time-major":
