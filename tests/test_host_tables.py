@@ -574,3 +574,17 @@ def test_choose_split_fills_the_slots(run):
         assert 1 <= nsplit <= max(1, nchunk // minchunk) and nsplit <= 4096
         nwg = -(-ndt // dpw) * nsplit
         assert grid_ % 8 == 0 and nwg <= grid_ < nwg + 8
+
+
+def test_choose_split_of_the_masked_tracer_shapes(run):
+    """The cuts test_gpu_masked_tracer_variants.py relies on, as launch_miss_tracer_project asks for them on 256 CUs
+    (slots = 2 * 256, four d-tiles per workgroup): cs8 has 217 chunks.  D = 1300 must keep ranges of at least 9 chunks
+    (whole groups on the clamp-free path of miss_tracer_project_kernel: three at a ring two deep), D = 21 the ranges of
+    4 or 5 of the small cases, and three chunks are one range."""
+    cases = np.array([(1300, 217, 512, 4, 4), (21, 217, 512, 4, 4), (3, 3, 512, 4, 4)], dtype=np.float64)
+    out = run("split", cases)["split"].reshape(-1, 4).astype(np.int64)
+    assert out[:, 0].tolist() == [82, 2, 1] and out[:, 3].tolist() == [4, 4, 4]
+    assert out[:, 1].tolist() == [24, 54, 1]
+    nchunk, nsplit = 217, int(out[0, 1])
+    ranges = [nchunk * (s + 1) // nsplit - nchunk * s // nsplit for s in range(nsplit)]
+    assert sum(ranges) == nchunk and min(ranges) >= 9
