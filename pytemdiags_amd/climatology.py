@@ -43,6 +43,16 @@ real pressure-level data varies in time (surface pressure moves), so the time me
 
 The ordinary masked run goes last: per-snapshot results, ``coverage``, native attributes and the plan's state are bit
 for bit those of the same object built without ``climatology``.  No tracers, no ``lat_bins``, no grouped means.
+
+Grouped and weighted means (``climatology=True, time_groups=g, time_weights=w``).  ``[.]_g`` is the weighted mean over
+the times labelled ``g``: ``sum_t w_t x_t / W_g`` with ``W_g = sum_t w_t`` over the group; a time labelled -1 is in no
+group.  Everything above holds per group: the group means of a field are ``[ncol][nlev][G]``, the engine's layout with
+``nt = G``, so the stationary part of all groups is ONE ordinary TEM run, the mean state and total fluxes are the
+grouped means of the per-snapshot zonal means, transient = total - stationary per group, and the three sets come out of
+three epilogues at ``nts = G`` with shape ``(lat, plev, G)``.  The device step is ``engine.Plan.time_sum_groups``
+(temxg_time_sum_groups), fused into the block loop with the block's ``t0`` and accumulating from the second block on;
+``GROUP_SUM_KERNEL`` chooses between it and ``torch.matmul`` with the ``[NT][G]`` weight matrix.  Not served: masked
+grouped means, tracer terms, the sharded runners, NetCDF output, more than 64 groups.
 """
 from __future__ import annotations
 
@@ -56,6 +66,12 @@ from . import _lib
 # torch.sum(x, -1, dtype=float64).  Set from tools/clim_bench.py (profiles/clim_bench_mi355x.json): the kernel is on
 # for a dtype where it is faster than torch at ne120 x 72 x 30.  The engine method is always the kernel.
 TIME_SUM_KERNEL = {"float64": True, "float32": True}
+
+# The same for the grouped sum of ``time_groups=`` / ``time_weights=`` (temxg_time_sum_groups against torch.matmul with
+# the [NT][G] weight matrix, after ``.double()`` for fp32 fields).  Set from tools/gclim_bench.py
+# (profiles/gclim_bench_mi355x.json): on for a dtype where the kernel is faster at ne120 x 72 x 30, two groups of 15.
+GROUP_SUM_KERNEL = {"float64": True, "float32": True}
+NG_MAX = 64
 
 FLUX_NAMES = ("upvpb", "upwappb", "vptpb")
 LINEAR_RESULTS = ("epfy", "epfz", "epdiv", "utendepfd")
@@ -113,6 +129,125 @@ def mean_time(time):
     return t[:1].copy()
 
 
+_MONTHS = ("Jan", "Feb", "Mar", "Apr", "May", "Jun", "Jul", "Aug", "Sep", "Oct", "Nov", "Dec")
+_SEASONS = ("DJF", "MAM", "JJA", "SON")
+
+
+def calendar_groups(time, by):
+    """Labels of a ``datetime64`` time axis by ``"month"``, ``"season"`` (DJF MAM JJA SON) or ``"year"`` ->
+    (int32 labels, the groups' names).  The groups are the keys present, in calendar order (years ascending); December
+    and the January after it both lie in DJF.  Pure numpy; ValueError for anything else."""
+    if by not in ("month", "season", "year"):
+        raise ValueError("time_groups must be 'month', 'season' or 'year' (or a sequence of labels), got %r" % (by,))
+    t = None if time is None else np.asarray(time)
+    if t is None or t.dtype.kind != "M" or t.ndim != 1:
+        raise ValueError("time_groups=%r needs a datetime64 time coordinate (time= for raw arrays)" % (by,))
+    if np.any(np.isnat(t)):
+        raise ValueError("time_groups=%r: the time coordinate holds NaT" % (by,))
+    months = t.astype("datetime64[M]").astype(np.int64)          # months since 1970-01
+    if by == "year":
+        key = months // 12 + 1970
+        names = None
+    elif by == "month":
+        key = months % 12
+        names = _MONTHS
+    else:
+        key = ((months % 12 + 1) % 12) // 3
+        names = _SEASONS
+    present = np.unique(key)
+    labels = np.searchsorted(present, key).astype(np.int32)
+    return labels, [str(int(k)) if names is None else names[int(k)] for k in present]
+
+
+def check_group_flags(time_groups, time_weights, climatology, missing):
+    """The part of the refusals that needs no sizes: either keyword without ``climatology=True`` or next to
+    ``missing="mask"``.  -> None when neither keyword is given, else ``(time_groups, time_weights)``."""
+    if time_groups is None and time_weights is None:
+        return None
+    if climatology is not True and not (isinstance(climatology, np.bool_) and bool(climatology)):
+        raise ValueError("time_groups / time_weights belong to the time-mean TEM: they need climatology=True")
+    if missing == "mask":
+        raise ValueError("time_groups / time_weights and missing='mask' exclude each other: masked grouped means are "
+                         "not served (climatology.py)")
+    return time_groups, time_weights
+
+
+class Groups:
+    """The resolved ``time_groups`` / ``time_weights`` of a record: ``labels`` (int32, -1 or 0..ng-1), ``weights``
+    (float64 or None: ones), ``ng``, ``names``, ``counts`` (times per group), ``wsum`` (total weight per group) and
+    ``time`` (the weighted mean time of each group)."""
+
+    def __init__(self, labels, weights, names, time):
+        self.labels, self.weights, self.names = labels, weights, names
+        self.ng = len(names)
+        w = np.ones(labels.size) if weights is None else weights
+        keep = labels >= 0
+        self.counts = np.bincount(labels[keep], minlength=self.ng).astype(np.int64)
+        self.wsum = np.bincount(labels[keep], weights=w[keep], minlength=self.ng).astype(np.float64)
+        if np.any(self.wsum <= 0):
+            raise ValueError("time_groups: group %d has no weight (every group needs a positive total weight)"
+                             % int(np.nonzero(self.wsum <= 0)[0][0]))
+        self.time = group_times(time, labels, w, self.ng)
+
+    def matrix(self):
+        """``Wm[t][g] = w_t [label_t == g]``, float64 ``(NT, ng)``: the weight matrix of the torch composition."""
+        w = np.ones(self.labels.size) if self.weights is None else self.weights
+        m = np.zeros((self.labels.size, self.ng))
+        keep = np.nonzero(self.labels >= 0)[0]
+        m[keep, self.labels[keep]] = w[keep]
+        return m
+
+
+def group_times(time, labels, w, ng):
+    """The weighted mean of a time coordinate per group (numbers, datetime64; anything else keeps the first entry of
+    each group)."""
+    t = np.asarray(time)
+    idx = [np.nonzero(labels == g)[0] for g in range(ng)]
+    if t.dtype.kind in "iuf":
+        return np.array([np.sum(w[i] * t[i].astype(np.float64)) / np.sum(w[i]) for i in idx])
+    if t.dtype.kind in "Mm":
+        out = []
+        for i in idx:
+            d = (t[i] - t[i[0]])
+            out.append(t[i[0]] + np.int64(np.rint(np.sum(w[i] * d.astype("int64")) / np.sum(w[i]))).astype(d.dtype))
+        return np.array(out, dtype=t.dtype)
+    return np.array([t[i[0]] for i in idx])
+
+
+def resolve_groups(time_groups, time_weights, nt, time):
+    """``time_groups`` / ``time_weights`` against a record of ``nt`` times with coordinate ``time`` -> ``Groups``.
+    ValueError for a wrong length, a label out of range, more than ``NG_MAX`` groups, a group with no weight, a weight
+    that is negative or not finite, and a calendar string without dates (no device needed)."""
+    nt = int(nt)
+    names = None
+    if isinstance(time_groups, str):
+        labels, names = calendar_groups(time, time_groups)
+    elif time_groups is None:
+        labels = np.zeros(nt, dtype=np.int32)
+    else:
+        g = np.asarray(time_groups)
+        if g.ndim != 1 or g.dtype.kind not in "iu":
+            raise ValueError("time_groups must be a one-dimensional integer sequence, 'month', 'season' or 'year'")
+        if g.size and (g.min() < -1 or g.max() >= 2 ** 31):
+            raise ValueError("time_groups: labels are -1 (left out) or 0..G-1, got %d" % (g.min() if g.min() < -1 else g.max()))
+        labels = g.astype(np.int32)
+    if labels.size != nt:
+        raise ValueError("time_groups has %d entries but the record has %d times" % (labels.size, nt))
+    ng = int(labels.max()) + 1 if labels.size else 0
+    if ng < 1:
+        raise ValueError("time_groups: no time belongs to a group")
+    if ng > NG_MAX:
+        raise ValueError("time_groups: %d groups, at most %d are served" % (ng, NG_MAX))
+    weights = None
+    if time_weights is not None:
+        weights = np.array(time_weights, dtype=np.float64)
+        if weights.ndim != 1 or weights.size != nt:
+            raise ValueError("time_weights has shape %s but the record has %d times" % (weights.shape, nt))
+        if not np.all(np.isfinite(weights)) or np.any(weights < 0):
+            raise ValueError("time_weights must be finite and not negative")
+    return Groups(labels, weights, list(range(ng)) if names is None else names, np.arange(nt) if time is None else time)
+
+
 class ResultSet:
     """One of ``total``, ``stationary``, ``transient``: the ten result methods, the sixteen zonal attributes and
     ``results()`` of ``TEMDiagnostics``, each ``(lat, plev, 1)``, wrapped and cast by the owner's own wrapping code."""
@@ -141,14 +276,22 @@ del _n
 class TEMClimatology:
     """``tem.climatology``: the three result sets of the time-mean TEM (module docstring).  ``nt`` is the number of
     snapshots averaged, ``time`` the mean of their time coordinate, ``time_sum_path`` ``"kernel"`` or ``"torch"``.
+    Grouped means (``time_groups=`` / ``time_weights=``): the sets are ``(lat, plev, G)``, ``time`` holds the weighted
+    mean time of each group, and ``groups`` (0..G-1), ``group_names`` (calendar names, else the integers),
+    ``group_counts`` (times per group) and ``group_weights`` (total weight per group) describe them.
     Masked climatology: ``time_coverage`` is the fraction of the snapshots whose masked zonal means are finite and
     ``stationary_coverage`` the zonal coverage of the run on the time-mean fields, both ``(lat, plev, 1)`` float64 and
     labelled like ``ub``; None otherwise."""
 
-    def __init__(self, owner, sets, nt, time, time_sum_path, time_coverage=None, stationary_coverage=None):
+    def __init__(self, owner, sets, nt, time, time_sum_path, time_coverage=None, stationary_coverage=None, groups=None):
         self.nt = int(nt)
         self.time = time
         self.time_sum_path = time_sum_path
+        if groups is not None:       # grouped means: the sets are (lat, plev, G), ``time`` the mean time of each group
+            self.groups = np.arange(groups.ng)
+            self.group_names = list(groups.names)
+            self.group_counts = groups.counts.copy()
+            self.group_weights = groups.wsum.copy()
         self._owner, self._tcov, self._scov = owner, time_coverage, stationary_coverage
         for name in SET_NAMES:
             res, zon = sets[name]
@@ -265,3 +408,69 @@ class MaskedBuilder(Builder):
             zm7[4:7] = fluxes[name]
             sets[name] = self.plan.tem_from_zonal_means(zm7, want_zonal=True)
         return TEMClimatology(self.owner, sets, self.nt, mean_time(self.owner.time), self.path, tcov, self.stat_cov)
+
+
+class GroupedBuilder(Builder):
+    """The builder of grouped and weighted means (module docstring): grouped sums at the block's ``t0`` instead of the
+    plain time sums, one stationary run over all groups (``nt = G``), grouped means on the zonal grid."""
+
+    def __init__(self, owner, plan, groups):
+        super().__init__(owner, plan)
+        work = str(owner._work_dtype).replace("torch.", "")
+        self.path = "kernel" if GROUP_SUM_KERNEL[work] else "torch"
+        self.groups = groups
+        self.t0 = 0
+        self._wm = None
+
+    def _sums(self, fields, t0, acc):
+        """Grouped sums of a block at ``t0`` -> list of fp64 ``[..][..][G]``; into ``acc`` (+=) when given."""
+        import torch
+        g = self.groups
+        if self.path == "kernel":
+            return self.plan.time_sum_groups(fields, g.labels, g.ng, g.weights, t0=t0, acc=acc, accumulate=acc is not None)
+        if self._wm is None:
+            self._wm = torch.as_tensor(g.matrix(), device=fields[0].device)
+        wm = self._wm[t0:t0 + int(fields[0].shape[-1])]
+        sums = [torch.matmul(x.double(), wm) for x in fields]
+        if acc is None:
+            return sums
+        for a, s in zip(acc, sums):
+            a += s
+        return acc
+
+    def add(self, fields):
+        fields = list(fields)
+        self.acc = self._sums(fields, self.t0, self.acc)
+        self.t0 += int(fields[0].shape[-1])
+        self.nt = self.t0
+
+    def _wsum(self, like):
+        import torch
+        return torch.as_tensor(self.groups.wsum, device=like.device)
+
+    def run_stationary(self):
+        """TEM of the group-mean fields, all groups in one run (fp64 whatever the work dtype): the plan is left set for
+        ``nt = G``."""
+        o, plan, G = self.owner, self.plan, self.groups.ng
+        means = [(a / self._wsum(a)).contiguous() for a in self.acc]
+        self.acc = None
+        plan.set_tem(o.NLEV, G, o._p_np, float(o.p0))
+        _, zon = plan.tem_run(*means, want_zonal=True)
+        if plan.status():
+            raise RuntimeError(_NAN_MESSAGE)
+        i0 = _lib.ZONAL_NAMES.index(FLUX_NAMES[0])
+        self.stat_flux = zon[i0:i0 + 3].clone()
+
+    def finish(self, zon_all):
+        """``zon_all``: ``[16][M][nlev][NT]`` of the ordinary run -> TEMClimatology with sets ``(lat, plev, G)``."""
+        _, M, nlev, nt = zon_all.shape
+        G = self.groups.ng
+        (acc,) = self._sums([zon_all[:7].reshape(7 * M * nlev, 1, nt)], 0, None)
+        total = (acc / self._wsum(acc)).reshape(7, M, nlev, G)
+        fluxes = {"total": total[4:7], "stationary": self.stat_flux, "transient": total[4:7] - self.stat_flux}
+        sets = {}
+        for name in SET_NAMES:
+            zm7 = total.clone()
+            zm7[4:7] = fluxes[name]
+            sets[name] = self.plan.tem_from_zonal_means(zm7, want_zonal=True)
+        return TEMClimatology(self.owner, sets, nt, self.groups.time, self.path, groups=self.groups)

@@ -23,6 +23,7 @@ using DpwValues = IntList<1, 2, 4>;              // d-tiles per workgroup
 using BinJValues = IntList<8, 10, 12>;           // Chebyshev terms per latitude bin
 using BinKPValues = IntList<16, 32, 48, 64>;     // K rounded up to a multiple of 16, binned form
 using SliceValues = IntList<2, 3, 4>;            // slices of 64 harmonics, large-L class path
+using GclimBoundValues = IntList<1, 4, 64>;      // groups present in a block, grouped time sum on long rows (64: any)
 using OsPairs = PairList<IntPair<7, 13>, IntPair<4, 8>, IntPair<2, 4>>;   // single sweep: (TBS, TBX)
 
 template <int V0, int... Vs, typename F>

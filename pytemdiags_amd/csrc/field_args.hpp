@@ -1,5 +1,6 @@
 // field_args.hpp -- host: the argument rules of the plan-free entry points (temxv_interp, temxl_to_engine,
-// temxi_records_to_pressure, temxc_time_sum, temxn_time_sum_valid), written once, and the level tables two of them share.  No HIP.
+// temxi_records_to_pressure, temxc_time_sum, temxn_time_sum_valid, temxg_time_sum_groups), written once, and the level
+// tables two of them share.  No HIP.
 // A check returns a Refusal, which is true when the call is refused; the entry point hands its code and message to
 // fail().  Every refusal here is TEMX_EINVAL.  tests/host/field_args_main.cpp runs this header under the sanitizers.
 #ifndef TEMX_FIELD_ARGS_HPP
@@ -68,6 +69,25 @@ inline Refusal check_window(int64_t nt_src, int64_t t0, int64_t ntb, bool remap 
   if (t0 < 0) return refuse("t0 must not be negative");
   if (ntb > nt_src || t0 > nt_src - ntb)
     return refuse("t0 + ntb = %lld exceeds nt_src = %lld", (long long)((uint64_t)t0 + (uint64_t)ntb), (long long)nt_src);
+  return {};
+}
+
+// the group arguments of temxg_time_sum_groups: ng groups, the block t0 .. t0 + nt (check_sizes has seen nt) of a record
+// of nt_record times, one label per time of the record (-1: left out) and one weight, or weight null: all ones
+inline Refusal check_groups(int ng, int ng_max, int64_t nt_record, int64_t t0, int64_t nt, const int32_t* label,
+                            const double* weight) {
+  if (ng < 1 || ng > ng_max) return refuse("ng must lie in 1..%d, got %d", ng_max, ng);
+  if (!label) return refuse("label_host is null");
+  if (t0 < 0) return refuse("t0 must not be negative");
+  if (nt_record > INT32_MAX) return refuse("sizes out of range (nt_record above 2^31 - 1)");
+  if (nt > nt_record || t0 > nt_record - nt)
+    return refuse("t0 + nt = %lld exceeds nt_record = %lld", (long long)((uint64_t)t0 + (uint64_t)nt), (long long)nt_record);
+  for (int64_t t = 0; t < nt_record; ++t)
+    if (label[t] < -1 || label[t] >= ng)
+      return refuse("label %lld is %d: labels lie in -1..%d", (long long)t, (int)label[t], ng - 1);
+  for (int64_t t = 0; weight && t < nt_record; ++t)
+    if (!std::isfinite(weight[t]) || weight[t] < 0.0)
+      return refuse("weight %lld must be finite and not negative", (long long)t);
   return {};
 }
 

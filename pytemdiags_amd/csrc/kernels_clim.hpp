@@ -55,11 +55,18 @@ struct ClimVec<float> {
   static __device__ __forceinline__ float get(const float4& v, int q) { return q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w; }
 };
 
+// the sum side of the plain time sum: the one written out in time_sum_staged_body
+struct ClimPlainSum {
+  static constexpr bool plain = true;
+};
+
 // one workgroup of the staged kernel, for a source of element type T.  lds: CLIM_LDS_BYTES, 16-byte aligned.
-template <typename T>
+// SUM: ClimPlainSum, or the sum side of another kernel that shares this load side (kernels_gclim.hpp): an object whose
+// sum(s, nr, r0, stride, acc, accumulate, tid) runs once the rows lie in LDS.
+template <typename T, typename SUM = ClimPlainSum>
 __device__ __forceinline__ void time_sum_staged_body(const T* __restrict__ src, double* __restrict__ acc, int64_t rows,
                                                      int nt, int rpb, int stride, int g, int accumulate,
-                                                     unsigned char* lds) {
+                                                     unsigned char* lds, const SUM& other = SUM{}) {
   using V = typename ClimVec<T>::type;
   constexpr int VN = ClimVec<T>::N;
   T* s = reinterpret_cast<T*>(lds);
@@ -107,6 +114,10 @@ __device__ __forceinline__ void time_sum_staged_body(const T* __restrict__ src, 
   }
   __syncthreads();
 
+  if constexpr (!SUM::plain) {
+    other.sum(s, nr, r0, stride, acc, accumulate, tid);
+    return;
+  }
   // ---- sum side: g lanes per row, rpb * g <= CLIM_THREADS, a row's lanes inside one wave ----
   const int r = tid / g, j = tid - r * g;
   double a = -0.0;

@@ -7,6 +7,7 @@
 #include "../../include/temx_clim.h"
 #include "../../include/temx_mtracer.h"
 #include "../../include/temx_nclim.h"
+#include "../../include/temx_gclim.h"
 
 #include <hip/hip_runtime.h>
 
@@ -39,6 +40,7 @@
 #include "kernels_ingest.hpp"
 #include "kernels_clim.hpp"
 #include "kernels_nclim.hpp"
+#include "kernels_gclim.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
 #include "bin_tables.hpp"
 #include "class_tables.hpp"
@@ -46,6 +48,7 @@
 #include "nclim_shapes.hpp"
 #include "dispatch.hpp"
 #include "field_args.hpp"
+#include "gclim_tables.hpp"
 #include "host_math.hpp"
 #include "launch_shapes.hpp"
 
@@ -1569,6 +1572,81 @@ static int launch_time_sum(const ClimPtrs& fp, int nf, int64_t rows, int64_t nt,
   } else {
     hipLaunchKernelGGL((time_sum_long_kernel<T>), dim3((unsigned)sh.nblk, (unsigned)nf), dim3(CLIM_THREADS), 0, st, fp, rows, nt,
                        accumulate);
+  }
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+// ---- the grouped time sum (include/temx_gclim.h, kernels_gclim.hpp) ----
+// The table of a record (labels, weights, ng) lives in a device buffer that is never written again once uploaded, as
+// the level tables of vert_tables do: every block of a blocked run finds it by content and touches no allocator.
+struct GclimTables {
+  int device;
+  GclimRecord rec;
+  unsigned char* dev;
+};
+static std::mutex g_gclim_mu;
+static std::vector<GclimTables> g_gclim_tabs;
+constexpr size_t GCLIM_TABLE_SETS = 8;
+
+static int gclim_tables(int device, int ng, int64_t nt_record, const int32_t* label, const double* weight, GclimTab* tb,
+                        GclimWindow* win, int64_t t0, int64_t nt) {
+  std::lock_guard<std::mutex> lk(g_gclim_mu);
+  const std::vector<unsigned char> key = gclim_key(ng, nt_record, label, weight);
+  const GclimTables* hit = nullptr;
+  for (const GclimTables& e : g_gclim_tabs)
+    if (e.device == device && e.rec.key == key) hit = &e;
+  if (!hit) {
+    if (g_gclim_tabs.size() >= GCLIM_TABLE_SETS) {   // hipFree waits for the kernels that may still read the oldest table
+      (void)hipFree(g_gclim_tabs.front().dev);
+      g_gclim_tabs.erase(g_gclim_tabs.begin());
+    }
+    GclimRecord rec = gclim_record(ng, nt_record, label, weight);
+    unsigned char* d = nullptr;
+    HIPCHK(hipMalloc(&d, rec.image.size()));
+    hipError_t e = hipMemcpy(d, rec.image.data(), rec.image.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return fail(TEMX_EHIP, "upload of the group table failed: %s", hipGetErrorString(e));
+    }
+    g_gclim_tabs.push_back(GclimTables{device, std::move(rec), d});
+    hit = &g_gclim_tabs.back();
+  }
+  const GclimRecord& r = hit->rec;
+  tb->w = reinterpret_cast<const double*>(hit->dev + r.off_w());
+  tb->sw = reinterpret_cast<const double*>(hit->dev + r.off_sw());
+  tb->lab = reinterpret_cast<const int32_t*>(hit->dev + r.off_lab());
+  tb->st = reinterpret_cast<const int32_t*>(hit->dev + r.off_st());
+  *win = gclim_window(r, t0, nt);
+  return TEMX_OK;
+}
+
+// one launch for the sources of one dtype; win.np >= 1
+template <typename T>
+static int launch_time_sum_groups(const ClimPtrs& fp, int nf, int64_t rows, int64_t nt, int64_t t0, const GclimTab& tb,
+                                  const GclimWindow& win, int accumulate, hipStream_t st) {
+  const GclimShape gs = gclim_shape(rows, nt, sizeof(T), win.np, win.ng);
+  const ClimShape& sh = gs.rows;
+  if (gs.nblk >= (int64_t(1) << 32) / CLIM_THREADS)   // HIP takes fewer than 2^32 threads per grid dimension
+    return fail(TEMX_EUNSUPPORTED, "too many rows for one launch (%lld workgroups): sum the fields in parts", (long long)gs.nblk);
+  const dim3 grid((unsigned)gs.nblk, (unsigned)nf);
+  if (sh.staged) {
+    if (gs.lds_bytes > (size_t)CLIM_LDS_BYTES || sh.stride < nt || (int64_t)sh.rpb * nt > (int64_t(1) << 30))
+      return fail(TEMX_EINTERNAL, "staged rows of the grouped time sum exceed their LDS budget");
+    hipLaunchKernelGGL((time_sum_groups_staged_kernel<T>), grid, dim3(CLIM_THREADS), 0, st, fp, rows, (int)nt, (int)t0, sh, tb,
+                       win, accumulate);
+  } else {
+    if (gs.lds_bytes > (size_t)GCLIM_LONG_LDS_BYTES || gs.rpw < 1 || gs.rpw > CLIM_LONG_ROWS)
+      return fail(TEMX_EINTERNAL, "long rows of the grouped time sum exceed their LDS budget");
+    dispatch(GclimBoundValues{}, gs.bound, [&](auto b) {
+      if constexpr (decltype(b)::value == GCLIM_NGMAX)
+        hipLaunchKernelGGL((time_sum_groups_long_lds_kernel<T>), grid, dim3(64 * gs.rpw), gs.lds_bytes, st, fp, rows, nt, t0, tb,
+                           win, accumulate, gs.rpw);
+      else
+        hipLaunchKernelGGL((time_sum_groups_long_kernel<T, decltype(b)::value>), grid, dim3(CLIM_THREADS), 0, st, fp, rows, nt,
+                           t0, tb, win, accumulate);
+      return 0;
+    });
   }
   HIPCHK(hipGetLastError());
   return TEMX_OK;
@@ -3830,6 +3908,40 @@ int temxn_time_sum_valid(int device, int nf, const void* const* src_host, int sr
   const int accumulate = (flags & TEMXN_ACCUMULATE) ? 1 : 0;
   if (src_dtype == TEMX_F64) return launch_time_sum_valid_nf<double>(fp, nf, common, rows, nt, accumulate, S_(stream));
   return launch_time_sum_valid_nf<float>(fp, nf, common, rows, nt, accumulate, S_(stream));
+} TEMX_CATCH
+
+// ---- grouped and weighted time means: the segmented sum over time (include/temx_gclim.h, kernels_gclim.hpp) ----
+int temxg_version(void) { return 100; }
+
+int temxg_time_sum_groups(int device, int nf, const void* const* src_host, const int* src_dtype_host, double* const* acc_host,
+                          int64_t ncol, int nlev, int64_t nt, int64_t nt_record, int64_t t0, int ng,
+                          const int32_t* label_host, const double* weight_host_or_null, int flags, void* stream) try {
+  ARGCHK(check_nf(nf, TEMXG_NF_MAX) | check_null(src_host, "src_host") | check_null(src_dtype_host, "src_dtype_host") |
+         check_null(acc_host, "acc_host") | check_sizes(ncol, nlev, nt, "nt") | check_flags(flags, TEMXG_ACCUMULATE));
+  ARGCHK(check_groups(ng, TEMXG_NG_MAX, nt_record, t0, nt, label_host, weight_host_or_null));
+  const int64_t rows = ncol * nlev;
+  ARGCHK(check_fields({nf, src_host, src_dtype_host, (size_t)rows * nt, (void* const*)acc_host, "acc", TEMX_F64, (size_t)rows * ng}));
+  // the fp64 and the fp32 sources go in a launch each: their rows are cut differently (clim_shapes.hpp)
+  ClimPtrs p64{}, p32{};
+  int n64 = 0, n32 = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (src_dtype_host[f] == TEMX_F64) p64.src[n64] = src_host[f], p64.acc[n64++] = acc_host[f];
+    else p32.src[n32] = src_host[f], p32.acc[n32++] = acc_host[f];
+  }
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = S_(stream);
+  const int accumulate = (flags & TEMXG_ACCUMULATE) ? 1 : 0;
+  GclimTab tb{};
+  GclimWindow win{};
+  int rc = gclim_tables(device, ng, nt_record, label_host, weight_host_or_null, &tb, &win, t0, nt);
+  if (rc) return rc;
+  if (win.np == 0) {   // no labelled time in the block: nothing to add, or all zeros
+    for (int f = 0; f < nf && !accumulate; ++f) HIPCHK(hipMemsetAsync(acc_host[f], 0, (size_t)rows * ng * sizeof(double), st));
+    return TEMX_OK;
+  }
+  if (n64 && (rc = launch_time_sum_groups<double>(p64, n64, rows, nt, t0, tb, win, accumulate, st))) return rc;
+  if (n32 && (rc = launch_time_sum_groups<float>(p32, n32, rows, nt, t0, tb, win, accumulate, st))) return rc;
+  return TEMX_OK;
 } TEMX_CATCH
 
 // ---- tracer TEM in missing-value mode (include/temx_mtracer.h, kernels_mtracer.hpp) ----

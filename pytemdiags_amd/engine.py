@@ -695,6 +695,60 @@ class Plan:
                                        flags, self._stream()))
         return acc, (cnt[0] if common else cnt)
 
+    # ---- grouped and weighted time means (include/temx_gclim.h) ----
+    def time_sum_groups(self, fields, labels, ngroups, weights=None, t0=0, acc=None, accumulate=False):
+        """Grouped, weighted sum over the last (time) axis of up to eight contiguous device tensors ``[ncol][nlev][nt]``,
+        fp64 or fp32 each (temxg_time_sum_groups): -> a list of fp64 ``[ncol][nlev][ngroups]`` tensors, ``acc`` itself
+        when given (``+=`` under ``accumulate``, which leaves the groups absent from the block untouched).  ``labels``
+        (-1: left out, else 0..ngroups-1) and ``weights`` (None: ones) are those of the whole record, host arrays; the
+        fields are its block at ``t0``.  All arithmetic is fp64; a (row, group) sum depends on the block's values,
+        labels and weights, ``nt`` and the dtype only."""
+        from . import _gclim
+        lib = _gclim.load()
+        fields = list(fields)
+        if not 1 <= len(fields) <= _gclim.NF_MAX:
+            raise ValueError("time_sum_groups takes 1..%d fields, got %d" % (_gclim.NF_MAX, len(fields)))
+        shape = tuple(fields[0].shape)
+        if len(shape) != 3:
+            raise ValueError("fields must be [ncol][nlev][nt], got %d dims" % len(shape))
+        ng = int(ngroups)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if lab.ndim != 1 or (w is not None and w.shape != lab.shape):
+            raise ValueError("labels and weights are one-dimensional and of the record's length")
+        fs = []
+        for x in fields:
+            if not isinstance(x, torch.Tensor):
+                raise TypeError("device tensors expected")
+            if x.device != self.device:
+                raise ValueError("tensor on %s, plan on %s" % (x.device, self.device))
+            if x.dtype not in _DT:
+                raise TypeError("dtype must be float64 or float32, got %s" % x.dtype)
+            if tuple(x.shape) != shape:
+                raise ValueError("field has shape %s, expected %s" % (tuple(x.shape), shape))
+            fs.append(x.contiguous())
+        out_shape = shape[:2] + (ng,)
+        if acc is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs acc=")
+            acc = list(torch.empty((len(fs),) + out_shape, dtype=torch.float64, device=self.device).unbind(0))
+        acc = list(acc)
+        if len(acc) != len(fs):
+            raise ValueError("acc has %d tensors for %d fields" % (len(acc), len(fs)))
+        for a in acc:
+            if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float64
+                    and tuple(a.shape) == out_shape and a.is_contiguous()):
+                raise ValueError("acc must hold contiguous float64 [ncol][nlev][ngroups] tensors on the plan's device")
+        n = len(fs)
+        src = (C.c_void_p * n)(*[x.data_ptr() for x in fs])
+        sdt = (C.c_int * n)(*[_DT[x.dtype] for x in fs])
+        dst = (C.c_void_p * n)(*[a.data_ptr() for a in acc])
+        check(lib.temxg_time_sum_groups(self.device_index, n, src, sdt, dst, shape[0], shape[1], shape[2], lab.size, int(t0),
+                                        ng, lab.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        None if w is None else w.ctypes.data_as(C.POINTER(C.c_double)),
+                                        _gclim.ACCUMULATE if accumulate else 0, self._stream()))
+        return acc
+
     def tem_from_zonal_means(self, zm7, want_zonal=False):
         """The epilogue of a TEM run on zonal means the caller supplies (temxc_tem_from_zonal_means): ``zm7`` is
         ``[7][M][nlev][nts]`` fp64 in the order ``ub vb thetab wapb upvpb upwappb vptpb``, ``nts`` any value >= 1.

@@ -42,11 +42,15 @@ class TEMDiagnostics:
                  dim_names=DEFAULT_DIMS, grid_name=None, zm_grid_name=None, map_save_dest=None,
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
-                 lat_bins=None, climatology=False, tracer_mask=None, min_time_coverage=None):
+                 lat_bins=None, climatology=False, tracer_mask=None, min_time_coverage=None, time_groups=None,
+                 time_weights=None):
         # ---- time-mean TEM (not in the reference; climatology.py): checked before anything touches the device ----
         self._want_climatology = clim.check_flag(climatology, missing, min_time_coverage)
         self.min_time_coverage = None if min_time_coverage is None else clim.time_coverage_value(min_time_coverage)
         self._climatology = None
+        # (grouped and weighted means: the sizes are checked in _config_dims, still before the device)
+        self._group_args = clim.check_group_flags(time_groups, time_weights, climatology, missing)
+        self._groups = None
         # ---- blocked run over the time axis (not in the reference): checked before anything touches the device ----
         self.time_block = layout.check_time_block(time_block)
         self._given_source = getattr(_pending, "source", None)
@@ -104,8 +108,11 @@ class TEMDiagnostics:
         self.block_timing = None
         self._clim = None
         if self._want_climatology:
-            self._clim = (clim.Builder(self, plan) if self.min_time_coverage is None
-                          else clim.MaskedBuilder(self, plan, self.min_time_coverage))
+            if self._groups is not None:
+                self._clim = clim.GroupedBuilder(self, plan, self._groups)
+            else:
+                self._clim = (clim.Builder(self, plan) if self.min_time_coverage is None
+                              else clim.MaskedBuilder(self, plan, self.min_time_coverage))
         if self.time_block is None and self._block_source is None:
             if self._clim is not None:      # time means and their TEM first: the ordinary run is the plan's last
                 self._clim.add(self._dev_fields)
@@ -293,7 +300,8 @@ class TEMDiagnostics:
         fitted under a mask of its own (valid where it, ``va`` and ``wap`` are finite; ``tracer_coverage``).
         ``climatology=True`` next to ``missing="mask"`` needs ``min_time_coverage=v`` (``0 < v <= 1``): the time-mean
         TEM over a mask that varies in time, a point kept where at least that fraction of the record is valid
-        (``climatology.py``).
+        (``climatology.py``).  ``time_groups=`` / ``time_weights=`` (grouped and weighted means, next to
+        ``climatology=True``) pass through as well and are checked against the record before any device work.
 
         Two orders of the axes are served, named by ``dims=`` for raw arrays and by ``.dims`` for labelled ones:
         ``(horz, vert, time)`` as above, and C-contiguous ``(time, vert, horz)`` with ``ps`` as ``(time, horz)`` --
@@ -311,6 +319,10 @@ class TEMDiagnostics:
         cls._check_tracer_mask(kw.get("tracer_mask"), kw.get("missing", "raise"), q)
         cls._check_lat_bins(kw.get("lat_bins"), kw.get("missing", "raise"))
         clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"), kw.get("min_time_coverage"))
+        if clim.check_group_flags(kw.get("time_groups"), kw.get("time_weights"), kw.get("climatology", False),
+                                  kw.get("missing", "raise")) is not None:
+            clim.resolve_groups(kw.get("time_groups"), kw.get("time_weights"),
+                                *cls._record_times(ua, kw.get("dims"), kw.get("dim_names", DEFAULT_DIMS), kw.get("time")))
         qs = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
         given = [ua, va, ta, wap] + qs
         if cls._model_level_order(given, kw.pop("dims", None), kw.get("dim_names", DEFAULT_DIMS)) == "time-major":
@@ -329,6 +341,25 @@ class TEMDiagnostics:
         if not raw:
             obj._kind = "xarray" if containers.is_xarray(ua) else "labeled"
         return obj
+
+    @staticmethod
+    def _record_times(first, dims, dim_names, time):
+        """(number of times, time coordinate) of a field as the constructor will see them, from its shape and labels
+        alone (host logic only): what ``time_groups`` / ``time_weights`` are checked against before any device work."""
+        tname = dim_names.get("time", DEFAULT_DIMS["time"])
+        if containers.is_labeled(first):
+            d, shape = tuple(first.dims), tuple(first.values.shape)
+            if tname in d:
+                try:
+                    time = np.asarray(containers.coord_of(first, tname))
+                except Exception:
+                    time = None
+        else:
+            shape = tuple(first.shape)
+            full = (dim_names["horz"], dim_names["vert"], tname)
+            d = tuple(dims) if dims is not None else full[:len(shape)]
+        nt = int(shape[d.index(tname)]) if tname in d and len(d) == len(shape) else 1
+        return nt, (np.asarray(time) if time is not None else np.arange(nt))
 
     @staticmethod
     def _model_level_order(given, dims, dim_names):
@@ -590,6 +621,10 @@ class TEMDiagnostics:
         self._coslat_zm = np.cos(self._lat_zm * np.pi / 180)                                  # :402
         self.lat, self.coslat = self._lat_zm, self._coslat_zm
         self.f = self._f_zm[:, np.newaxis, np.newaxis]
+
+        # ---- grouped and weighted time means (climatology.py): labels and weights against the record, on the host ----
+        if self._group_args is not None:
+            self._groups = clim.resolve_groups(*self._group_args, self.NT, self.time)
 
         # ---- device residency: contiguous [ncol][plev][time], one dtype ----
         dts = {v.dtype for v in vals.values()}
