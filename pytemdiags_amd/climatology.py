@@ -42,7 +42,8 @@ real pressure-level data varies in time (surface pressure moves), so the time me
     the epilogue as it does in a masked run.
 
 The ordinary masked run goes last: per-snapshot results, ``coverage``, native attributes and the plan's state are bit
-for bit those of the same object built without ``climatology``.  No tracers, no ``lat_bins``, no grouped means.
+for bit those of the same object built without ``climatology``.  No tracers, no ``lat_bins``; grouped means of masked
+fields have a keyword of their own (``min_group_coverage``, below).
 
 Grouped and weighted means (``climatology=True, time_groups=g, time_weights=w``).  ``[.]_g`` is the weighted mean over
 the times labelled ``g``: ``sum_t w_t x_t / W_g`` with ``W_g = sum_t w_t`` over the group; a time labelled -1 is in no
@@ -51,8 +52,28 @@ group.  Everything above holds per group: the group means of a field are ``[ncol
 grouped means of the per-snapshot zonal means, transient = total - stationary per group, and the three sets come out of
 three epilogues at ``nts = G`` with shape ``(lat, plev, G)``.  The device step is ``engine.Plan.time_sum_groups``
 (temxg_time_sum_groups), fused into the block loop with the block's ``t0`` and accumulating from the second block on;
-``GROUP_SUM_KERNEL`` chooses between it and ``torch.matmul`` with the ``[NT][G]`` weight matrix.  Not served: masked
-grouped means, tracer terms, the sharded runners, NetCDF output, more than 64 groups.
+``GROUP_SUM_KERNEL`` chooses between it and ``torch.matmul`` with the ``[NT][G]`` weight matrix.  Not served: tracer
+terms, the sharded runners, NetCDF output, more than 64 groups.
+
+Masked grouped means (``climatology=True, missing="mask", min_group_coverage=v`` next to ``time_groups=`` and / or
+``time_weights=``; ``0 < v <= 1``).  The two contracts above, per group.  With ``n_g`` the times labelled ``g`` (whatever
+their weight) and ``need_g = max(1, ceil(v n_g - 1e-9))``:
+
+  * group-mean fields  per (column, level, group), the weighted sum over the times of the group that are valid under
+    the common mask of the four fields, divided by the sum of their weights: NaN where fewer than ``need_g`` of them
+    are valid or their weights sum to zero.  The threshold goes by the count, which is exact; the division by the
+    weight.  Sums, weight sums and counts come from ``engine.Plan.time_sum_groups_valid(common=True)``
+    (temxw_time_sum_groups_valid), fused into the block loop at the block's ``t0`` and accumulating from the second
+    block on; division and thresholding are torch on ``[ncol][nlev][G]``.
+  * stationary fluxes  of ONE masked TEM run at ``nt = G`` on those fp64 mean fields under the object's
+    ``min_coverage``; its zonal coverage is ``tem.climatology.stationary_coverage``, ``(lat, plev, G)``.
+  * mean state and total fluxes   one ``time_sum_groups_valid(common=False)`` call on the seven per-snapshot masked
+    zonal means viewed as ``[7 M nlev rows][NT]``, the same threshold rule; ``time_coverage`` is the count over
+    ``n_g``, a true division, ``(lat, plev, G)``.
+  * transient = total - stationary per group (a definition, as in the masked climatology); three epilogues at
+    ``nts = G``.
+``time_weights`` alone gives one weighted masked group.  ``min_time_coverage`` belongs to the ungrouped masked mean and
+is refused next to ``min_group_coverage``.  No tracers, no ``lat_bins``, no ``ncol`` sharding.
 """
 from __future__ import annotations
 
@@ -87,11 +108,14 @@ _NAN_MESSAGE = ("Variable has nans! Spectral zonal averager cannot handle nans; 
                 "please replace or remove them")
 
 
-def check_flag(climatology, missing, min_time_coverage=None):
+def check_flag(climatology, missing, min_time_coverage=None, min_group_coverage=None):
     """``climatology`` as a bool; ValueError for anything else, next to ``missing="mask"`` unless ``min_time_coverage``
-    opts into the masked contract, and for a ``min_time_coverage`` without both or outside (0, 1] (no device needed)."""
+    opts into the masked contract (or ``min_group_coverage``, which ``check_group_coverage`` has seen, into the masked
+    grouped one), and for a ``min_time_coverage`` without both or outside (0, 1] (no device needed)."""
     if not isinstance(climatology, (bool, np.bool_)):
         raise ValueError("climatology must be True or False, got %r" % (climatology,))
+    if min_group_coverage is not None and min_time_coverage is None:
+        return bool(climatology)
     if min_time_coverage is not None:
         if not (climatology and missing == "mask"):
             raise ValueError("min_time_coverage belongs to the masked climatology: it needs climatology=True and "
@@ -109,6 +133,34 @@ def time_coverage_value(min_time_coverage):
     if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 < float(v) <= 1.0:
         raise ValueError("min_time_coverage must be a number in (0, 1], got %r" % (v,))
     return float(v)
+
+
+def check_group_coverage(min_group_coverage, climatology, missing, time_groups, time_weights, min_time_coverage=None):
+    """``min_group_coverage`` as a float in (0, 1], or None when it is not given.  ValueError for a value that is no
+    number in (0, 1], without ``climatology=True`` and ``missing="mask"``, without ``time_groups`` / ``time_weights``,
+    and next to ``min_time_coverage`` (no device needed)."""
+    v = min_group_coverage
+    if v is None:
+        return None
+    if not isinstance(climatology, (bool, np.bool_)):
+        raise ValueError("climatology must be True or False, got %r" % (climatology,))
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 < float(v) <= 1.0:
+        raise ValueError("min_group_coverage must be a number in (0, 1], got %r" % (v,))
+    if not (climatology and missing == "mask"):
+        raise ValueError("min_group_coverage belongs to the masked grouped means: it needs climatology=True and "
+                         "missing='mask'")
+    if time_groups is None and time_weights is None:
+        raise ValueError("min_group_coverage belongs to the masked grouped means: it needs time_groups= and/or "
+                         "time_weights= (min_time_coverage serves the ungrouped masked mean)")
+    if min_time_coverage is not None:
+        raise ValueError("min_group_coverage and min_time_coverage exclude each other: the first is the threshold of "
+                         "the masked grouped means, the second that of the ungrouped masked mean")
+    return float(v)
+
+
+def group_times_needed(min_group_coverage, counts):
+    """``need_g = max(1, ceil(v n_g - 1e-9))`` per group, with ``n_g`` the times labelled g whatever their weight."""
+    return np.array([times_needed(min_group_coverage, n) for n in counts], dtype=np.float64)
 
 
 def times_needed(min_time_coverage, nt):
@@ -159,14 +211,15 @@ def calendar_groups(time, by):
     return labels, [str(int(k)) if names is None else names[int(k)] for k in present]
 
 
-def check_group_flags(time_groups, time_weights, climatology, missing):
+def check_group_flags(time_groups, time_weights, climatology, missing, min_group_coverage=None):
     """The part of the refusals that needs no sizes: either keyword without ``climatology=True`` or next to
-    ``missing="mask"``.  -> None when neither keyword is given, else ``(time_groups, time_weights)``."""
+    ``missing="mask"`` (unless ``min_group_coverage``, which ``check_group_coverage`` has seen, opts into the masked
+    grouped means).  -> None when neither keyword is given, else ``(time_groups, time_weights)``."""
     if time_groups is None and time_weights is None:
         return None
     if climatology is not True and not (isinstance(climatology, np.bool_) and bool(climatology)):
         raise ValueError("time_groups / time_weights belong to the time-mean TEM: they need climatology=True")
-    if missing == "mask":
+    if missing == "mask" and min_group_coverage is None:
         raise ValueError("time_groups / time_weights and missing='mask' exclude each other: masked grouped means are "
                          "not served (climatology.py)")
     return time_groups, time_weights
@@ -281,7 +334,8 @@ class TEMClimatology:
     ``group_counts`` (times per group) and ``group_weights`` (total weight per group) describe them.
     Masked climatology: ``time_coverage`` is the fraction of the snapshots whose masked zonal means are finite and
     ``stationary_coverage`` the zonal coverage of the run on the time-mean fields, both ``(lat, plev, 1)`` float64 and
-    labelled like ``ub``; None otherwise."""
+    labelled like ``ub``; None otherwise.  Masked grouped means: both are ``(lat, plev, G)``, ``time_coverage`` the
+    fraction of each group's times."""
 
     def __init__(self, owner, sets, nt, time, time_sum_path, time_coverage=None, stationary_coverage=None, groups=None):
         self.nt = int(nt)
@@ -474,3 +528,69 @@ class GroupedBuilder(Builder):
             zm7[4:7] = fluxes[name]
             sets[name] = self.plan.tem_from_zonal_means(zm7, want_zonal=True)
         return TEMClimatology(self.owner, sets, nt, self.groups.time, self.path, groups=self.groups)
+
+
+class MaskedGroupedBuilder(Builder):
+    """The builder of masked grouped means (module docstring): grouped sums over the valid times with their weight sums
+    and counts at the block's ``t0``, one masked stationary run over all groups (``nt = G``), counted, weighted and
+    thresholded group means on the zonal grid."""
+
+    def __init__(self, owner, plan, groups, min_group_coverage):
+        super().__init__(owner, plan)
+        self.path = "kernel"
+        self.groups = groups
+        self.v = float(min_group_coverage)
+        self.need = group_times_needed(self.v, groups.counts)
+        self.t0 = 0
+        self.wsum = self.cnt = None
+        self.stat_cov = None
+
+    def add(self, fields):
+        fields = list(fields)
+        g = self.groups
+        first = self.acc is None
+        self.acc, self.wsum, self.cnt = self.plan.time_sum_groups_valid(
+            fields, g.labels, g.ng, g.weights, t0=self.t0, acc=self.acc, wsum=self.wsum, cnt=self.cnt, accumulate=not first,
+            common=True)
+        self.t0 += int(fields[0].shape[-1])
+        self.nt = self.t0
+
+    def _mean(self, acc, wsum, cnt):
+        """``acc / wsum`` where at least ``need_g`` times are valid and carry weight, NaN elsewhere (``[..][G]``)."""
+        import torch
+        need = torch.as_tensor(self.need, device=acc.device)
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=acc.device)
+        return torch.where((cnt >= need) & (wsum > 0), acc / wsum, nan)
+
+    def run_stationary(self):
+        """Masked TEM of the group-mean fields, all groups in one run (fp64 whatever the work dtype): the plan is left
+        set for ``nt = G``."""
+        o, plan, G = self.owner, self.plan, self.groups.ng
+        means = [self._mean(a, self.wsum, self.cnt).contiguous() for a in self.acc]
+        self.acc = self.wsum = self.cnt = None
+        plan.set_tem(o.NLEV, G, o._p_np, float(o.p0))
+        _, zon = plan.tem_run(*means, want_zonal=True)
+        self.stat_cov = plan.coverage().reshape(o.ZM_N, o.NLEV, G)
+        if plan.status():
+            raise RuntimeError(_NAN_MESSAGE)
+        i0 = _lib.ZONAL_NAMES.index(FLUX_NAMES[0])
+        self.stat_flux = zon[i0:i0 + 3].clone()
+
+    def finish(self, zon_all):
+        """``zon_all``: ``[16][M][nlev][NT]`` of the ordinary masked run -> TEMClimatology with sets ``(lat, plev, G)``."""
+        import torch
+        _, M, nlev, nt = zon_all.shape
+        g = self.groups
+        G = g.ng
+        (acc,), (wsum,), (cnt,) = self.plan.time_sum_groups_valid([zon_all[:7].reshape(7 * M * nlev, 1, nt)], g.labels, G,
+                                                                  g.weights, common=False)
+        total = self._mean(acc, wsum, cnt).reshape(7, M, nlev, G)
+        # (tensor by tensor: a true division, so that 3 of 5 is 0.6 and not 3 * 0.2)
+        tcov = torch.true_divide(cnt.reshape(7, M, nlev, G)[0], torch.as_tensor(g.counts.astype(np.float64), device=cnt.device))
+        fluxes = {"total": total[4:7], "stationary": self.stat_flux, "transient": total[4:7] - self.stat_flux}
+        sets = {}
+        for name in SET_NAMES:
+            zm7 = total.clone()
+            zm7[4:7] = fluxes[name]
+            sets[name] = self.plan.tem_from_zonal_means(zm7, want_zonal=True)
+        return TEMClimatology(self.owner, sets, nt, g.time, self.path, tcov, self.stat_cov, groups=g)

@@ -1,6 +1,6 @@
 // field_args.hpp -- host: the argument rules of the plan-free entry points (temxv_interp, temxl_to_engine,
-// temxi_records_to_pressure, temxc_time_sum, temxn_time_sum_valid, temxg_time_sum_groups), written once, and the level
-// tables two of them share.  No HIP.
+// temxi_records_to_pressure, temxc_time_sum, temxn_time_sum_valid, temxg_time_sum_groups,
+// temxw_time_sum_groups_valid), written once, and the level tables two of them share.  No HIP.
 // A check returns a Refusal, which is true when the call is refused; the entry point hands its code and message to
 // fail().  Every refusal here is TEMX_EINVAL.  tests/host/field_args_main.cpp runs this header under the sanitizers.
 #ifndef TEMX_FIELD_ARGS_HPP
@@ -165,6 +165,30 @@ inline Refusal check_sum_valid(int nf, const void* const* src, int dtype, size_t
       if (extents_overlap(cnt[f], out_bytes, acc[g], out_bytes)) return refuse("cnt %d overlaps acc %d", f, g);
       if (g < f && extents_overlap(cnt[f], out_bytes, cnt[g], out_bytes)) return refuse("cnt %d overlaps cnt %d", f, g);
     }
+  return {};
+}
+
+// temxw_time_sum_groups_valid: as check_sum_valid, with two further sets of nextra fp64 outputs (nf, or 1 under a common
+// mask), the weight sums and the counts.  Each obeys the rules of an accumulator and overlaps no source and no other output.
+// (tests/host/mgclim_shapes_main.cpp runs this check under the sanitizers.)
+inline Refusal check_sum_groups_valid(int nf, const void* const* src, int dtype, size_t src_elems, double* const* acc,
+                                      double* const* wsum, double* const* cnt, int nextra, size_t out_elems) {
+  if (Refusal r = check_sum_valid(nf, src, dtype, src_elems, acc, cnt, nextra, out_elems)) return r;
+  const size_t out_bytes = out_elems * sizeof(double);
+  for (int f = 0; f < nextra; ++f) {
+    if (!wsum[f]) return refuse("wsum %d is null", f);
+    if ((uintptr_t)wsum[f] % sizeof(double)) return refuse("wsum %d is not aligned to its element size", f);
+  }
+  for (int f = 0; f < nextra; ++f) {
+    for (int g = 0; g < nf; ++g) {
+      if (extents_overlap(wsum[f], out_bytes, src[g], src_elems * dtype_size(dtype))) return refuse("wsum %d overlaps src %d", f, g);
+      if (extents_overlap(wsum[f], out_bytes, acc[g], out_bytes)) return refuse("wsum %d overlaps acc %d", f, g);
+    }
+    for (int g = 0; g < nextra; ++g) {
+      if (extents_overlap(wsum[f], out_bytes, cnt[g], out_bytes)) return refuse("wsum %d overlaps cnt %d", f, g);
+      if (g < f && extents_overlap(wsum[f], out_bytes, wsum[g], out_bytes)) return refuse("wsum %d overlaps wsum %d", f, g);
+    }
+  }
   return {};
 }
 

@@ -8,6 +8,7 @@
 #include "../../include/temx_mtracer.h"
 #include "../../include/temx_nclim.h"
 #include "../../include/temx_gclim.h"
+#include "../include/temx_mgclim.h"
 
 #include <hip/hip_runtime.h>
 
@@ -41,6 +42,7 @@
 #include "kernels_clim.hpp"
 #include "kernels_nclim.hpp"
 #include "kernels_gclim.hpp"
+#include "kernels_mgclim.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
 #include "bin_tables.hpp"
 #include "class_tables.hpp"
@@ -51,6 +53,7 @@
 #include "gclim_tables.hpp"
 #include "host_math.hpp"
 #include "launch_shapes.hpp"
+#include "mgclim_shapes.hpp"
 
 using namespace temx;
 
@@ -1677,6 +1680,42 @@ static int launch_time_sum_valid_nf(const NclimPtrs& fp, int nf, bool common, in
   if (!common) return launch_time_sum_valid<T, 1>(fp, nf, rows, nt, accumulate, st);
   if (nf <= 4) return launch_time_sum_valid<T, 4>(fp, nf, rows, nt, accumulate, st);
   return launch_time_sum_valid<T, NCLIM_NFMAX>(fp, nf, rows, nt, accumulate, st);
+}
+
+// ---- the masked grouped time sum (../include/temx_mgclim.h): NFT fields per workgroup, 1 in own-mask mode; win.np >= 1 ----
+template <typename T, int NFT>
+static int launch_time_sum_groups_valid(int device, const MgclimPtrs& fp, int nf, int64_t rows, int64_t nt, int64_t t0,
+                                        const GclimTab& tb, const GclimWindow& win, int accumulate, hipStream_t st) {
+  const int nfs = NFT == 1 ? 1 : nf;
+  const MgclimShape sh = mgclim_shape(rows, nt, sizeof(T), nfs, win.np);
+  if (sh.nblk >= (int64_t(1) << 32) / MGCLIM_THREADS)   // HIP takes fewer than 2^32 threads per grid dimension
+    return fail(TEMX_EUNSUPPORTED, "too many rows for one launch (%lld workgroups): sum the fields in parts", (long long)sh.nblk);
+  const dim3 grid((unsigned)sh.nblk, NFT == 1 ? (unsigned)nf : 1u);
+  if (sh.staged) {
+    if (sh.lds_bytes > (size_t)NCLIM_LDS_BYTES || sh.stride < nt || sh.rpb < 1 || sh.rpb > MGCLIM_THREADS)
+      return fail(TEMX_EINTERNAL, "staged rows of the masked grouped time sum exceed their LDS budget");
+    return launch<time_sum_groups_valid_staged_kernel<T, NFT>>(grid, dim3(MGCLIM_THREADS), 0, st, fp, nf, rows, (int)nt, (int)t0,
+                                                               sh.rpb, sh.stride, tb, win, accumulate);
+  }
+  if (sh.lds_bytes > (size_t)MGCLIM_LONG_LDS_BYTES || sh.rpw < 1 || sh.rpw > NCLIM_LONG_ROWS)
+    return fail(TEMX_EINTERNAL, "long rows of the masked grouped time sum exceed their LDS budget");
+  return dispatch(GclimBoundValues{}, sh.bound, [&](auto b) {
+    if constexpr (decltype(b)::value == GCLIM_NGMAX)
+      return launch_lds<time_sum_groups_valid_long_lds_kernel<T, NFT>, MGCLIM_LONG_LDS_BYTES>(
+          device, grid, dim3(64 * sh.rpw), sh.lds_bytes, st, fp, nf, rows, nt, t0, tb, win, accumulate, sh.rpw, sh.batch);
+    else
+      return launch<time_sum_groups_valid_long_kernel<T, NFT, decltype(b)::value>>(grid, dim3(MGCLIM_THREADS), 0, st, fp, nf, rows,
+                                                                                   nt, t0, tb, win, accumulate);
+  });
+}
+
+template <typename T>
+static int launch_time_sum_groups_valid_nf(int device, const MgclimPtrs& fp, int nf, bool common, int64_t rows, int64_t nt,
+                                           int64_t t0, const GclimTab& tb, const GclimWindow& win, int accumulate,
+                                           hipStream_t st) {
+  if (!common) return launch_time_sum_groups_valid<T, 1>(device, fp, nf, rows, nt, t0, tb, win, accumulate, st);
+  if (nf <= 4) return launch_time_sum_groups_valid<T, 4>(device, fp, nf, rows, nt, t0, tb, win, accumulate, st);
+  return launch_time_sum_groups_valid<T, MGCLIM_NFMAX>(device, fp, nf, rows, nt, t0, tb, win, accumulate, st);
 }
 
 extern "C" {
@@ -3942,6 +3981,48 @@ int temxg_time_sum_groups(int device, int nf, const void* const* src_host, const
   if (n64 && (rc = launch_time_sum_groups<double>(p64, n64, rows, nt, t0, tb, win, accumulate, st))) return rc;
   if (n32 && (rc = launch_time_sum_groups<float>(p32, n32, rows, nt, t0, tb, win, accumulate, st))) return rc;
   return TEMX_OK;
+} TEMX_CATCH
+
+// ---- masked grouped time means: the grouped sum over the valid times (../include/temx_mgclim.h, kernels_mgclim.hpp) ----
+int temxw_version(void) { return 100; }
+
+int temxw_time_sum_groups_valid(int device, int nf, const void* const* src_host, int src_dtype, double* const* acc_host,
+                                double* const* wsum_host, double* const* cnt_host, int64_t ncol, int nlev, int64_t nt,
+                                int64_t nt_record, int64_t t0, int ng, const int32_t* label_host,
+                                const double* weight_host_or_null, int flags, void* stream) try {
+  ARGCHK(check_nf(nf, TEMXW_NF_MAX) | check_null(src_host, "src_host") | check_null(acc_host, "acc_host") |
+         check_null(wsum_host, "wsum_host") | check_null(cnt_host, "cnt_host") | check_dtype(src_dtype, "src_dtype") |
+         check_sizes(ncol, nlev, nt, "nt") | check_flags(flags, TEMXW_ACCUMULATE | TEMXW_COMMON_MASK));
+  ARGCHK(check_groups(ng, TEMXW_NG_MAX, nt_record, t0, nt, label_host, weight_host_or_null));
+  const int64_t rows = ncol * nlev;
+  const bool common = (flags & TEMXW_COMMON_MASK) != 0;
+  const int nextra = common ? 1 : nf;
+  ARGCHK(check_sum_groups_valid(nf, src_host, src_dtype, (size_t)rows * nt, acc_host, wsum_host, cnt_host, nextra,
+                                (size_t)rows * ng));
+  MgclimPtrs fp{};
+  for (int f = 0; f < nf; ++f)
+    fp.src[f] = src_host[f], fp.acc[f] = acc_host[f], fp.wsum[f] = wsum_host[common ? 0 : f], fp.cnt[f] = cnt_host[common ? 0 : f];
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = S_(stream);
+  const int accumulate = (flags & TEMXW_ACCUMULATE) ? 1 : 0;
+  GclimTab tb{};
+  GclimWindow win{};
+  int rc = gclim_tables(device, ng, nt_record, label_host, weight_host_or_null, &tb, &win, t0, nt);
+  if (rc) return rc;
+  if (win.np == 0) {   // no labelled time in the block: nothing to add, or all zeros
+    const size_t bytes = (size_t)rows * ng * sizeof(double);
+    for (int f = 0; f < nf && !accumulate; ++f) {
+      HIPCHK(hipMemsetAsync(acc_host[f], 0, bytes, st));
+      if (f < nextra) {
+        HIPCHK(hipMemsetAsync(wsum_host[f], 0, bytes, st));
+        HIPCHK(hipMemsetAsync(cnt_host[f], 0, bytes, st));
+      }
+    }
+    return TEMX_OK;
+  }
+  if (src_dtype == TEMX_F64)
+    return launch_time_sum_groups_valid_nf<double>(device, fp, nf, common, rows, nt, t0, tb, win, accumulate, st);
+  return launch_time_sum_groups_valid_nf<float>(device, fp, nf, common, rows, nt, t0, tb, win, accumulate, st);
 } TEMX_CATCH
 
 // ---- tracer TEM in missing-value mode (include/temx_mtracer.h, kernels_mtracer.hpp) ----

@@ -749,6 +749,74 @@ class Plan:
                                         _gclim.ACCUMULATE if accumulate else 0, self._stream()))
         return acc
 
+    # ---- masked grouped time means (pytemdiags_amd/include/temx_mgclim.h) ----
+    def time_sum_groups_valid(self, fields, labels, ngroups, weights=None, t0=0, acc=None, wsum=None, cnt=None,
+                              accumulate=False, common=True):
+        """Grouped, weighted sum over the valid (finite) times of up to eight contiguous device tensors
+        ``[ncol][nlev][nt]`` of one dtype, fp64 or fp32 (temxw_time_sum_groups_valid): per (row, group) the sum of
+        ``w * x`` over the valid times of the group, the sum of their weights and their number.  ``common=True``: a time
+        of a row is valid iff it is finite in every field, and the fields share one weight sum and one count.
+        -> (a list of fp64 ``[ncol][nlev][ngroups]`` sums, the weight sums, the counts: one fp64 tensor each under
+        ``common``, else a list of them); ``acc`` / ``wsum`` / ``cnt`` themselves when given (``+=`` under
+        ``accumulate``, which needs all three and leaves the groups absent from the block untouched).  ``labels``
+        (-1: left out, else 0..ngroups-1) and ``weights`` (None: ones) are those of the whole record, host arrays; the
+        fields are its block at ``t0``.  The order of the additions is that of ``time_sum_groups``."""
+        from . import _mgclim
+        lib = _mgclim.load()
+        fields = list(fields)
+        if not 1 <= len(fields) <= _mgclim.NF_MAX:
+            raise ValueError("time_sum_groups_valid takes 1..%d fields, got %d" % (_mgclim.NF_MAX, len(fields)))
+        shape = tuple(fields[0].shape)
+        if len(shape) != 3:
+            raise ValueError("fields must be [ncol][nlev][nt], got %d dims" % len(shape))
+        ng = int(ngroups)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if lab.ndim != 1 or (w is not None and w.shape != lab.shape):
+            raise ValueError("labels and weights are one-dimensional and of the record's length")
+        fs = []
+        for x in fields:
+            if not isinstance(x, torch.Tensor):
+                raise TypeError("device tensors expected")
+            if x.device != self.device:
+                raise ValueError("tensor on %s, plan on %s" % (x.device, self.device))
+            if x.dtype not in _DT:
+                raise TypeError("dtype must be float64 or float32, got %s" % x.dtype)
+            if x.dtype != fields[0].dtype:
+                raise TypeError("the fields of one call share a dtype, got %s and %s" % (fields[0].dtype, x.dtype))
+            if tuple(x.shape) != shape:
+                raise ValueError("field has shape %s, expected %s" % (tuple(x.shape), shape))
+            fs.append(x.contiguous())
+        n = len(fs)
+        if accumulate and (acc is None or wsum is None or cnt is None):
+            raise ValueError("accumulate=True needs acc=, wsum= and cnt=")
+        out_shape = shape[:2] + (ng,)
+
+        def outputs(given, count, what):
+            if given is None:
+                return list(torch.empty((count,) + out_shape, dtype=torch.float64, device=self.device).unbind(0))
+            given = [given] if isinstance(given, torch.Tensor) else list(given)
+            if len(given) != count:
+                raise ValueError("%s has %d tensors, expected %d" % (what, len(given), count))
+            for a in given:
+                if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float64
+                        and tuple(a.shape) == out_shape and a.is_contiguous()):
+                    raise ValueError("%s must hold contiguous float64 [ncol][nlev][ngroups] tensors on the plan's device" % what)
+            return given
+        acc = outputs(acc, n, "acc")
+        wsum = outputs(wsum, 1 if common else n, "wsum")
+        cnt = outputs(cnt, 1 if common else n, "cnt")
+        src = (C.c_void_p * n)(*[x.data_ptr() for x in fs])
+        dst = (C.c_void_p * n)(*[a.data_ptr() for a in acc])
+        wdst = (C.c_void_p * n)(*([a.data_ptr() for a in wsum] + [None] * (n - len(wsum))))
+        cdst = (C.c_void_p * n)(*([a.data_ptr() for a in cnt] + [None] * (n - len(cnt))))
+        flags = (_mgclim.ACCUMULATE if accumulate else 0) | (_mgclim.COMMON_MASK if common else 0)
+        check(lib.temxw_time_sum_groups_valid(self.device_index, n, src, _DT[fs[0].dtype], dst, wdst, cdst, shape[0], shape[1],
+                                              shape[2], lab.size, int(t0), ng, lab.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              None if w is None else w.ctypes.data_as(C.POINTER(C.c_double)), flags,
+                                              self._stream()))
+        return acc, (wsum[0] if common else wsum), (cnt[0] if common else cnt)
+
     def tem_from_zonal_means(self, zm7, want_zonal=False):
         """The epilogue of a TEM run on zonal means the caller supplies (temxc_tem_from_zonal_means): ``zm7`` is
         ``[7][M][nlev][nts]`` fp64 in the order ``ub vb thetab wapb upvpb upwappb vptpb``, ``nts`` any value >= 1.

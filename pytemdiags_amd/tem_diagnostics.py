@@ -43,13 +43,15 @@ class TEMDiagnostics:
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
                  lat_bins=None, climatology=False, tracer_mask=None, min_time_coverage=None, time_groups=None,
-                 time_weights=None):
+                 time_weights=None, min_group_coverage=None):
         # ---- time-mean TEM (not in the reference; climatology.py): checked before anything touches the device ----
-        self._want_climatology = clim.check_flag(climatology, missing, min_time_coverage)
+        self.min_group_coverage = clim.check_group_coverage(min_group_coverage, climatology, missing, time_groups,
+                                                            time_weights, min_time_coverage)
+        self._want_climatology = clim.check_flag(climatology, missing, min_time_coverage, self.min_group_coverage)
         self.min_time_coverage = None if min_time_coverage is None else clim.time_coverage_value(min_time_coverage)
         self._climatology = None
         # (grouped and weighted means: the sizes are checked in _config_dims, still before the device)
-        self._group_args = clim.check_group_flags(time_groups, time_weights, climatology, missing)
+        self._group_args = clim.check_group_flags(time_groups, time_weights, climatology, missing, self.min_group_coverage)
         self._groups = None
         # ---- blocked run over the time axis (not in the reference): checked before anything touches the device ----
         self.time_block = layout.check_time_block(time_block)
@@ -108,7 +110,9 @@ class TEMDiagnostics:
         self.block_timing = None
         self._clim = None
         if self._want_climatology:
-            if self._groups is not None:
+            if self._groups is not None and self.min_group_coverage is not None:
+                self._clim = clim.MaskedGroupedBuilder(self, plan, self._groups, self.min_group_coverage)
+            elif self._groups is not None:
                 self._clim = clim.GroupedBuilder(self, plan, self._groups)
             else:
                 self._clim = (clim.Builder(self, plan) if self.min_time_coverage is None
@@ -301,7 +305,8 @@ class TEMDiagnostics:
         ``climatology=True`` next to ``missing="mask"`` needs ``min_time_coverage=v`` (``0 < v <= 1``): the time-mean
         TEM over a mask that varies in time, a point kept where at least that fraction of the record is valid
         (``climatology.py``).  ``time_groups=`` / ``time_weights=`` (grouped and weighted means, next to
-        ``climatology=True``) pass through as well and are checked against the record before any device work.
+        ``climatology=True``) pass through as well and are checked against the record before any device work; next to
+        ``missing="mask"`` they need ``min_group_coverage=v`` (``0 < v <= 1``), the masked grouped means.
 
         Two orders of the axes are served, named by ``dims=`` for raw arrays and by ``.dims`` for labelled ones:
         ``(horz, vert, time)`` as above, and C-contiguous ``(time, vert, horz)`` with ``ps`` as ``(time, horz)`` --
@@ -318,9 +323,11 @@ class TEMDiagnostics:
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (kw["missing"],))
         cls._check_tracer_mask(kw.get("tracer_mask"), kw.get("missing", "raise"), q)
         cls._check_lat_bins(kw.get("lat_bins"), kw.get("missing", "raise"))
-        clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"), kw.get("min_time_coverage"))
+        mgc = clim.check_group_coverage(kw.get("min_group_coverage"), kw.get("climatology", False), kw.get("missing", "raise"),
+                                        kw.get("time_groups"), kw.get("time_weights"), kw.get("min_time_coverage"))
+        clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"), kw.get("min_time_coverage"), mgc)
         if clim.check_group_flags(kw.get("time_groups"), kw.get("time_weights"), kw.get("climatology", False),
-                                  kw.get("missing", "raise")) is not None:
+                                  kw.get("missing", "raise"), mgc) is not None:
             clim.resolve_groups(kw.get("time_groups"), kw.get("time_weights"),
                                 *cls._record_times(ua, kw.get("dims"), kw.get("dim_names", DEFAULT_DIMS), kw.get("time")))
         qs = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
