@@ -9,6 +9,7 @@
 #include "../../include/temx_nclim.h"
 #include "../../include/temx_gclim.h"
 #include "../include/temx_mgclim.h"
+#include "../include/temx_wave.h"
 
 #include <hip/hip_runtime.h>
 
@@ -43,6 +44,7 @@
 #include "kernels_nclim.hpp"
 #include "kernels_gclim.hpp"
 #include "kernels_mgclim.hpp"
+#include "kernels_wave.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
 #include "bin_tables.hpp"
 #include "class_tables.hpp"
@@ -54,6 +56,7 @@
 #include "host_math.hpp"
 #include "launch_shapes.hpp"
 #include "mgclim_shapes.hpp"
+#include "wave_tables.hpp"
 
 using namespace temx;
 
@@ -446,13 +449,14 @@ static int launch_project(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int
 // B[n] = (addend ? addend : 0) + sum over the nsplit slabs; slab sp starts at partial + sp * stride
 // (stride < 0: the slabs are dense, stride = n)
 // map: where entry idx of the sum goes (default: B[idx]; time slices for a reduce-scatter: kernels.hpp, SliceMap)
+// flag: where a non-finite sum is reported (default: the plan's own, which temx_status reads)
 static int launch_reduce(temx_plan* pl, const double* partial, int nsplit, int64_t n, double* B,
                          hipStream_t st, int64_t stride = -1, const double* addend = nullptr,
-                         const SliceMap& map = SliceMap()) {
+                         const SliceMap& map = SliceMap(), int* flag = nullptr) {
   if (stride < 0) stride = n;
+  if (flag == nullptr) flag = static_cast<int*>(pl->flag.p);
   if (nsplit <= 16 && n >= 32768) {   // many entries, few slabs: one thread per entry (same bits)
     const dim3 grid((unsigned)((n + 255) / 256));
-    int* flag = static_cast<int*>(pl->flag.p);
     if (nsplit <= 2)
       hipLaunchKernelGGL(reduce_partials_flat_kernel<2>, grid, dim3(256), 0, st, partial, nsplit, stride, n, addend, B, flag, map);
     else if (nsplit <= 4)
@@ -466,7 +470,7 @@ static int launch_reduce(temx_plan* pl, const double* partial, int nsplit, int64
   }
   const int64_t blocks = (n + 15) / 16;
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)blocks), dim3(256), 0, st, partial, nsplit, stride, n,
-                     addend, B, static_cast<int*>(pl->flag.p), map);
+                     addend, B, flag, map);
   HIPCHK(hipGetLastError());
   return TEMX_OK;
 }
@@ -1716,6 +1720,167 @@ static int launch_time_sum_groups_valid_nf(int device, const MgclimPtrs& fp, int
   if (!common) return launch_time_sum_groups_valid<T, 1>(device, fp, nf, rows, nt, t0, tb, win, accumulate, st);
   if (nf <= 4) return launch_time_sum_groups_valid<T, 4>(device, fp, nf, rows, nt, t0, tb, win, accumulate, st);
   return launch_time_sum_groups_valid<T, MGCLIM_NFMAX>(device, fp, nf, rows, nt, t0, tb, win, accumulate, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// zonal wavenumbers (../include/temx_wave.h, kernels_wave.hpp, wave_tables.hpp)
+// ------------------------------------------------------------------------------------------------
+struct WaveM {
+  int m = 0;
+  WaveShape sh;
+  DevBuf yblk;      // the deflated basis as 4x4 blocks, sh.gstride blocks per group of 4 rows
+  DevBuf pz;        // [M][ndeg] Pbar_l^m at the output latitudes
+  DevBuf ginv;      // [Kc][Kc] inverse of Gm = Ym^T Ym, from its Cholesky factor
+};
+
+struct temxk_wave {
+  temx_plan* pl = nullptr;
+  int device = 0;
+  std::vector<WaveM> ms;
+  int kc_max = 0;
+  DevBuf lat, lon, lat_out;     // radians
+  DevBuf partial, B, C, flag;   // slabs of the sweep, sums [nf][Kc][D], coefficients [nf][Kc][D], the reduction's own flag
+  bool timing = false;          // temxk_wave_timing: events around the projection sweeps of temxk_wave_fluxes
+  std::vector<TimedLaunch> timed;
+  void drop_events() {
+    for (auto& tl : timed) {
+      (void)hipEventDestroy(tl.a);
+      (void)hipEventDestroy(tl.b);
+    }
+    timed.clear();
+  }
+  ~temxk_wave() {
+    drop_events();
+    for (WaveM& w : ms) {
+      w.yblk.release();
+      w.pz.release();
+      w.ginv.release();
+    }
+    for (DevBuf* b : {&lat, &lon, &lat_out, &partial, &B, &C, &flag}) b->release();
+  }
+};
+
+// The wave projection: a workgroup's 4 waves are the 4 fields of one d-tile (NF = 4), or 4 d-tiles of one field (NF = 1).
+// Waves per SIMD by the blocks in the accumulators: up to 16 the instantiations of the plan's own sweeps (ProjCfgE /
+// ProjCfg1), beyond 16 two -- at three, 25 and 32 blocks spill registers.
+template <int NF, int TBv> struct WaveCfg {
+  static constexpr int WPS = NF == 1 ? ProjCfg1::WPS : (TBv <= 16 ? ProjCfgE::WPS : 2), DPW = NF == 1 ? 4 : 1;
+};
+template <int NF>
+static Split wave_split(const temx_plan* pl, int64_t D, int tb) {
+  const int wps = tb <= 16 ? WaveCfg<NF, 16>::WPS : WaveCfg<NF, 32>::WPS;
+  return choose_split(D, pl->nchunk, wps * pl->num_cu, WaveCfg<NF, 16>::DPW);
+}
+
+// the deterministic slab sum of launch_reduce, reporting into the wave state's own flag (temxk_wave_status; the plan's is
+// plan state)
+static int wave_reduce(temxk_wave* w, const double* partial, int nsplit, int64_t stride, int64_t n, double* B, hipStream_t st) {
+  return launch_reduce(w->pl, partial, nsplit, n, B, st, stride, nullptr, SliceMap(), static_cast<int*>(w->flag.p));
+}
+
+// B[NF][Kc][D] = Ymd^T {fields}: the generic project sweep on the wave basis, one sweep per WAVE_SLICE_TB blocks of columns
+template <int NF>
+static int wave_sweep(temxk_wave* w, const WaveM& wm, const FieldPtrs<NF>& fp, int dtype, int64_t D, const double* colscale,
+                      int sfield, double* B, hipStream_t st) {
+  temx_plan* pl = w->pl;
+  const WaveShape& sh = wm.sh;
+  size_t need = 0;
+  for (int sl = 0; sl < sh.nslice; ++sl)
+    need = std::max(need, (size_t)wave_split<NF>(pl, D, wave_slice_tb(sh, sl)).nsplit * NF * wave_slice_cols(sh, sl) * D * 8);
+  int rc = w->partial.ensure(need);
+  if (rc) return rc;
+  for (int sl = 0; sl < sh.nslice; ++sl) {
+    const int Ks = wave_slice_cols(sh, sl);
+    const Split sp = wave_split<NF>(pl, D, wave_slice_tb(sh, sl));
+    rc = by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      return dispatch(WaveTBValues{}, wave_slice_tb(sh, sl), [&](auto tb) {
+        constexpr int TBv = decltype(tb)::value;
+        return launch<project_kernel<T, NF, 1, TBv, 2, WaveCfg<NF, TBv>::WPS>>(
+            dim3(sp.grid), dim3(256), 0, st, fp, pl->N, D, Ks, (const double*)wm.yblk.d(), sh.gstride, WAVE_SLICE_TB * sl,
+            pl->nchunk, colscale, sfield, w->partial.d(), sp.nsplit, sp.ndt);
+      });
+    });
+    if (rc) return rc;
+    if (sh.nslice == 1) return wave_reduce(w, w->partial.d(), sp.nsplit, (int64_t)NF * Ks * D, (int64_t)NF * Ks * D, B, st);
+    for (int f = 0; f < NF; ++f)     // the slice's rows of every field, to their place in B
+      if ((rc = wave_reduce(w, w->partial.d() + (int64_t)f * Ks * D, sp.nsplit, (int64_t)NF * Ks * D, (int64_t)Ks * D,
+                            B + ((int64_t)f * sh.Kc + 4 * WAVE_SLICE_TB * sl) * D, st)))
+        return rc;
+  }
+  return TEMX_OK;
+}
+
+static int wave_solve(const WaveM& wm, int nf, int64_t D, const double* B, double* C, hipStream_t st) {
+  hipLaunchKernelGGL(wave_solve_kernel, dim3((unsigned)((D + 63) / 64), (unsigned)((wm.sh.Kc + 3) / 4), (unsigned)nf), dim3(256),
+                     0, st, B, wm.sh.Kc, D, (const double*)wm.ginv.d(), C);
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+static int wave_ensure(temxk_wave* w, int nf, int64_t D) {
+  int rc;
+  if ((rc = w->B.ensure((size_t)nf * w->kc_max * D * 8))) return rc;
+  return w->C.ensure((size_t)nf * w->kc_max * D * 8);
+}
+
+// one wavenumber: basis, zonal table, Gm and its inverse, deflation by the plan's native zonal-mean operator
+static int wave_build_m(temxk_wave* w, WaveM& wm) {
+  temx_plan* pl = w->pl;
+  const WaveShape& sh = wm.sh;
+  const int m = wm.m, L = pl->L, Kc = sh.Kc;
+  const int64_t N = pl->N, npad = pl->nchunk * 16;
+  double r = (2.0 * m + 1.0) / (4.0 * M_PI);
+  for (int k = 1; k <= m; ++k) r *= (2.0 * k - 1.0) / (2.0 * k);
+  const double pmm_norm = ((m & 1) ? -1.0 : 1.0) * std::sqrt(2.0) * std::sqrt(r);
+  int rc;
+  if ((rc = wm.yblk.ensure((size_t)npad * sh.kpad * 8))) return rc;
+  if ((rc = wm.pz.ensure((size_t)pl->M * sh.ndeg * 8))) return rc;
+  if ((rc = wm.ginv.ensure((size_t)Kc * Kc * 8))) return rc;
+  DevBuf Ym, Z;                 // row-major basis and its native zonal mean: build time only
+  struct Free {
+    DevBuf &a, &b;
+    ~Free() { a.release(); b.release(); }
+  } free_{Ym, Z};
+  if ((rc = Ym.ensure((size_t)N * Kc * 8))) return rc;
+  if ((rc = Z.ensure((size_t)N * Kc * 8))) return rc;
+  hipLaunchKernelGGL(wave_basis_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, nullptr, (const double*)w->lat.d(),
+                     (const double*)w->lon.d(), N, npad, m, L, pmm_norm, sh.gstride, Ym.d(), wm.yblk.d());
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(wave_ztable_kernel, dim3((unsigned)((pl->M + 255) / 256)), dim3(256), 0, nullptr,
+                     (const double*)w->lat_out.d(), pl->M, m, L, pmm_norm, wm.pz.d());
+  HIPCHK(hipGetLastError());
+  // Gm = Ym^T Ym: the sweep with the basis itself as the field (D = Kc), before the blocks are deflated
+  if ((rc = wave_ensure(w, 1, Kc))) return rc;
+  FieldPtrs<1> fp;
+  fp.p[0] = Ym.p;
+  if ((rc = wave_sweep<1>(w, wm, fp, TEMX_F64, Kc, nullptr, -1, w->B.d(), nullptr))) return rc;
+  std::vector<double> G((size_t)Kc * Kc), Gi((size_t)Kc * Kc), F;
+  HIPCHK(hipMemcpy(G.data(), w->B.p, G.size() * 8, hipMemcpyDeviceToHost));
+  for (double v : G)
+    if (!std::isfinite(v)) return fail(TEMX_ERANK, "zonal wavenumber m = %d: the Gram matrix of the basis is not finite", m);
+  if (const int piv = wave_cholesky(G.data(), Kc, F))
+    return fail(TEMX_ERANK, "zonal wavenumber m = %d: the Gram matrix of its %d basis columns is not positive definite "
+                "(pivot %d): the grid does not resolve this wavenumber at L = %d", m, Kc, piv - 1, L);
+  wave_inverse_from_factor(F, Kc, Gi.data());
+  HIPCHK(hipMemcpy(wm.ginv.p, Gi.data(), Gi.size() * 8, hipMemcpyHostToDevice));
+  // Ymd = Ym - P Ym with the plan's own operator (operator workspace of the plan only)
+  if ((rc = temx_zonal_mean(pl, Ym.p, TEMX_F64, Kc, Z.d(), 1, nullptr))) return rc;
+  hipLaunchKernelGGL(wave_deflate_kernel, dim3((unsigned)((N * Kc + 255) / 256)), dim3(256), 0, nullptr, (const double*)Ym.d(),
+                     (const double*)Z.d(), N, Kc, sh.gstride, wm.yblk.d());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return TEMX_OK;
+}
+
+static int wave_plan_refused(const temx_plan* pl) {
+  if (pl->weighted) return fail(TEMX_EUNSUPPORTED, "zonal wavenumbers are not available on a plan in weights mode");
+  if (miss_mode(pl)) return fail(TEMX_EUNSUPPORTED, "zonal wavenumbers are not available in missing-value mode (TEMX_OPT_MISSING = 1)");
+  if (bin_mode(pl)) return fail(TEMX_EUNSUPPORTED, "zonal wavenumbers are not available while latitude bins are in effect (TEMX_OPT_LAT_BINS)");
+  if (pl->ext_G)
+    return fail(TEMX_EUNSUPPORTED, "zonal wavenumbers are not available on a plan finalised with a Gram matrix from outside "
+                "(an ncol-sharded job): the fit runs over all columns of the grid");
+  return TEMX_OK;
 }
 
 extern "C" {
@@ -4095,6 +4260,180 @@ int temxm_tracer_eddy(temx_plan* pl, const void* q, const void* va, const void* 
   f3.p[0] = q; f3.p[1] = va; f3.p[2] = wap;
   TracerEddyOut eo{{ptrs3_host[0], ptrs3_host[1], ptrs3_host[2]}};
   return launch_miss_tracer_native(pl, f3, dtype, eo, S_(stream));
+} TEMX_CATCH
+
+// ---- zonal wavenumbers: wave-m components and eddy fluxes (../include/temx_wave.h, kernels_wave.hpp) ----
+int temxk_version(void) { return 100; }
+
+int temxk_wave_create(temxk_wave** out, temx_plan* pl, const double* lon_deg_host, int nm, const int* m_host) try {
+  if (!out) return fail(TEMX_EINVAL, "null argument");
+  *out = nullptr;
+  if (!pl) return fail(TEMX_EINVAL, "null plan");
+  if (!pl->finalized) return fail(TEMX_ESTATE, "plan not finalised");
+  char msg[256];
+  if (const int code = wave_check_args(pl->L, pl->N, lon_deg_host, nm, m_host, msg, sizeof msg)) return fail(code, "%s", msg);
+  if (int rc = wave_plan_refused(pl)) return rc;
+  HIPCHK(hipSetDevice(pl->device));
+  HIPCHK(hipDeviceSynchronize());
+  temxk_wave* w = new temxk_wave();
+  w->pl = pl;
+  w->device = pl->device;
+  auto bail = [&](int code) {
+    delete w;
+    return code;
+  };
+  const double d2r = M_PI / 180.0;
+  std::vector<double> lat((size_t)pl->N), lon((size_t)pl->N), lat_out((size_t)pl->M);
+  for (int64_t i = 0; i < pl->N; ++i) lat[(size_t)i] = pl->h_lat[(size_t)i] * d2r, lon[(size_t)i] = lon_deg_host[i] * d2r;
+  for (int j = 0; j < pl->M; ++j) lat_out[(size_t)j] = pl->lat_out_deg[(size_t)j] * d2r;
+  int rc, zero = 0;
+  if ((rc = upload(w->lat, lat)) || (rc = upload(w->lon, lon)) || (rc = upload(w->lat_out, lat_out)) ||
+      (rc = upload(w->flag, &zero, sizeof zero)))
+    return bail(rc);
+  w->ms.resize((size_t)nm);
+  for (int i = 0; i < nm; ++i) {
+    w->ms[(size_t)i].m = m_host[i];
+    w->ms[(size_t)i].sh = wave_shape(pl->L, m_host[i]);
+    w->kc_max = std::max(w->kc_max, w->ms[(size_t)i].sh.Kc);
+  }
+  for (WaveM& wm : w->ms)
+    if ((rc = wave_build_m(w, wm))) return bail(rc);
+  *out = w;
+  return TEMX_OK;
+} TEMX_CATCH
+
+void temxk_wave_destroy(temxk_wave* w) {
+  if (!w) return;
+  (void)hipSetDevice(w->device);   // (the plan may be gone already)
+  (void)hipDeviceSynchronize();
+  delete w;
+}
+
+int64_t temxk_wave_workspace_bytes(const temxk_wave* w) {
+  if (!w) return 0;
+  size_t n = w->lat.bytes + w->lon.bytes + w->lat_out.bytes + w->partial.bytes + w->B.bytes + w->C.bytes + w->flag.bytes;
+  for (const WaveM& wm : w->ms) n += wm.yblk.bytes + wm.pz.bytes + wm.ginv.bytes;
+  return (int64_t)n;
+}
+
+int temxk_wave_project(temxk_wave* w, int mi, int nf, const void* const* fields_host, const int* dtype_host, int64_t D,
+                       double* parts, double* coef_or_null, void* stream) try {
+  if (!w || !fields_host || !dtype_host || !parts) return fail(TEMX_EINVAL, "null argument");
+  if (mi < 0 || mi >= (int)w->ms.size()) return fail(TEMX_EINVAL, "mi must lie in 0..%d, got %d", (int)w->ms.size() - 1, mi);
+  if (nf < 1 || nf > WAVE_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", WAVE_NF_MAX, nf);
+  for (int f = 0; f < nf; ++f) {
+    if (!fields_host[f]) return fail(TEMX_EINVAL, "field %d is null", f);
+    if (dtype_host[f] != TEMX_F64 && dtype_host[f] != TEMX_F32) return bad_dtype();
+  }
+  if (D < 1 || D >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "D must be in [1, 2^28)");
+  temx_plan* pl = w->pl;
+  if (int rc = wave_plan_refused(pl)) return rc;
+  HIPCHK(hipSetDevice(pl->device));
+  hipStream_t st = S_(stream);
+  const WaveM& wm = w->ms[(size_t)mi];
+  const int64_t KD = (int64_t)wm.sh.Kc * D, MD = (int64_t)pl->M * D;
+  int rc;
+  if ((rc = wave_ensure(w, 1, D))) return rc;
+  for (int f = 0; f < nf; ++f) {
+    FieldPtrs<1> fp;
+    fp.p[0] = fields_host[f];
+    double* C = coef_or_null ? coef_or_null + f * KD : w->C.d();
+    if ((rc = wave_sweep<1>(w, wm, fp, dtype_host[f], D, nullptr, -1, w->B.d(), st))) return rc;
+    if ((rc = wave_solve(wm, 1, D, w->B.d(), C, st))) return rc;
+    hipLaunchKernelGGL(wave_parts_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)pl->M, 1), dim3(256), 0, st,
+                       (const double*)C, wm.sh.ndeg, pl->M, D, (const double*)wm.pz.d(), parts + f * 2 * MD);
+    HIPCHK(hipGetLastError());
+  }
+  return TEMX_OK;
+} TEMX_CATCH
+
+int temxk_wave_fluxes(temxk_wave* w, const void* ua, const void* va, const void* ta, const void* wap, int dtype,
+                      double* flux, double* parts_or_null, void* stream) try {
+  if (!w || !ua || !va || !ta || !wap || !flux) return fail(TEMX_EINVAL, "null argument");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
+  temx_plan* pl = w->pl;
+  if (int rc = tem_ready(pl)) return rc;
+  if (int rc = wave_plan_refused(pl)) return rc;
+  HIPCHK(hipSetDevice(pl->device));
+  hipStream_t st = S_(stream);
+  const int64_t D = pl->D, MD = (int64_t)pl->M * D;
+  int rc;
+  if ((rc = wave_ensure(w, 4, D))) return rc;
+  const FieldPtrs<4> fp = four(ua, va, ta, wap);
+  for (size_t i = 0; i < w->ms.size(); ++i) {
+    const WaveM& wm = w->ms[i];
+    // theta = T (p0/p)^kappa fused into the load of field 2, as in temx_tem_stage1
+    TimedLaunch tl{nullptr, nullptr};
+    bool timed = false;
+    if (w->timing && w->timed.size() < kMaxTimedLaunches) {
+      timed = hipEventCreate(&tl.a) == hipSuccess;
+      if (timed && hipEventCreate(&tl.b) != hipSuccess) {
+        (void)hipEventDestroy(tl.a);
+        timed = false;
+      }
+      if (timed) (void)hipEventRecord(tl.a, st);
+    }
+    rc = wave_sweep<4>(w, wm, fp, dtype, D, pl->colscale.d(), 2, w->B.d(), st);
+    if (timed) {
+      (void)hipEventRecord(tl.b, st);
+      w->timed.push_back(tl);
+    }
+    if (rc) return rc;
+    if ((rc = wave_solve(wm, 4, D, w->B.d(), w->C.d(), st))) return rc;
+    hipLaunchKernelGGL(wave_flux_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)pl->M), dim3(256), 0, st,
+                       (const double*)w->C.d(), wm.sh.ndeg, pl->M, D, (const double*)wm.pz.d(), flux + (int64_t)i * 3 * MD,
+                       parts_or_null ? parts_or_null + (int64_t)i * 8 * MD : (double*)nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  return TEMX_OK;
+} TEMX_CATCH
+
+// Synchronises the stream and reports whether a non-finite value reached the sums of temxk_wave_project / temxk_wave_fluxes
+// since the last call (as temx_status does for the plan's own sums; the two flags are separate).
+int temxk_wave_status(temxk_wave* w, int* nonfinite, void* stream) try {
+  if (!w || !nonfinite) return fail(TEMX_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(w->device));
+  HIPCHK(hipStreamSynchronize(S_(stream)));
+  int f = 0, zero = 0;
+  HIPCHK(hipMemcpy(&f, w->flag.p, sizeof f, hipMemcpyDeviceToHost));
+  if (f) HIPCHK(hipMemcpy(w->flag.p, &zero, sizeof zero, hipMemcpyHostToDevice));
+  *nonfinite = f != 0;
+  return TEMX_OK;
+} TEMX_CATCH
+
+// wave_shape of wave_tables.hpp, for callers that size buffers or report the stored bytes (no device, no state)
+int temxk_wave_shape(int L, int m, int* shape6_host) try {
+  if (!shape6_host) return fail(TEMX_EINVAL, "null argument");
+  if (L < 1 || L > 511 || m < 1 || m > L) return fail(TEMX_EINVAL, "L must lie in 1..511 and m in 1..L, got L = %d, m = %d", L, m);
+  const WaveShape s = wave_shape(L, m);
+  const int v[6] = {s.ndeg, s.Kc, s.nslice, s.tb_last, s.gstride, s.kpad};
+  std::copy(v, v + 6, shape6_host);
+  return TEMX_OK;
+} TEMX_CATCH
+
+// measurement helper (tools/wave_bench.py; not on the product path): events around the projection sweeps (sweep and slab
+// reduction) of temxk_wave_fluxes.  Enabling or disabling drops the events recorded so far.
+int temxk_wave_timing(temxk_wave* w, int enable) try {
+  if (!w) return fail(TEMX_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(w->device));
+  w->drop_events();
+  w->timing = enable != 0;
+  return TEMX_OK;
+} TEMX_CATCH
+
+int temxk_wave_timing_read(temxk_wave* w, double* sum_ms, int* launches) try {
+  if (!w || !sum_ms || !launches) return fail(TEMX_EINVAL, "null argument");
+  HIPCHK(hipSetDevice(w->device));
+  double tot = 0.0;
+  for (auto& tl : w->timed) {
+    HIPCHK(hipEventSynchronize(tl.b));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, tl.a, tl.b));
+    tot += ms;
+  }
+  *sum_ms = tot;
+  *launches = (int)w->timed.size();
+  return TEMX_OK;
 } TEMX_CATCH
 
 }  // extern "C"

@@ -45,8 +45,14 @@ class sph_zonal_averager:
 
     def __init__(self, lat, lat_out, L, weights=None, grid_name=None, grid_out_name=None,
                  ncoldim="ncol", overwrite=False, save_dest=None, debug=False, logfile=None,
-                 device=None, fp32_fields=False, missing="raise", min_coverage=0.5, *, lat_bins=None):
+                 device=None, fp32_fields=False, missing="raise", min_coverage=0.5, *, lat_bins=None, lon=None):
         self.L = L
+        # (not in the reference's signature) lon=: the longitudes of the native columns in degrees, for sph_wave
+        self._lon = None
+        self._waves = {}
+        if lon is not None:
+            from . import waves
+            self._lon = waves.check_lon(lon, len(_as_numpy(lat)))
         # (not in the reference's signature) missing="mask": non-finite values are missing points of a masked fit
         # instead of an error; outputs whose coverage is below min_coverage are NaN (include/temx.h)
         if missing not in _lib.MISSING_MODES:
@@ -175,6 +181,7 @@ class sph_zonal_averager:
         weighted = self._w_raw is not None
         if weighted and len(self._w_raw) != len(self.lat):
             raise RuntimeError("number of weights must equal number of native grid latitudes!")   # :353-354
+        self._close_waves()
         if self._plan is not None:
             self._plan.close()
         self._cache = {}
@@ -266,6 +273,62 @@ class sph_zonal_averager:
             attrs = dict(DEFAULT_LAT_ATTRS)
         attrs["long_name"] = "zonal mean of {}".format(name)                                 # :275
         return containers.make_like(kind, out_vals, dims, coords, name, attrs)
+
+    # ---- zonal wavenumbers (not in the reference; waves.py, include/temx_wave.h) ----
+    def _close_waves(self):
+        for st in getattr(self, "_waves", {}).values():
+            st.close()
+        self._waves = {}
+
+    def sph_wave(self, A, m):
+        """The wave-``m`` component of ``A`` on ``lat_out``: ``(cos part, sin part)``, each typed, shaped and labelled
+        like ``sph_zonal_mean(A)``; the component is ``cos part * cos(m lon) + sin part * sin(m lon)``.  A least-squares
+        fit of the eddy ``A - sph_zonal_mean_native(A)`` on ``Pbar_l^m(sin lat) cos / sin(m lon)``, ``l = m..L``, over
+        every column.  Needs ``lon=`` at construction; ``m`` an integer in 1..L."""
+        import torch
+        from . import waves
+        if self._lon is None:
+            raise ValueError("sph_wave needs lon=: build the averager with the longitudes of the native columns")
+        if self._w_raw is not None:
+            raise ValueError("sph_wave and a weights averager exclude each other: the wave fit is unweighted")
+        if self.missing == "mask" or self._lat_bins:
+            raise ValueError("sph_wave and %s exclude each other (not served yet)"
+                             % ("missing='mask'" if self.missing == "mask" else "lat_bins"))
+        (m,) = waves.check_wavenumbers([m], self.L)
+        if self._plan is None:
+            raise RuntimeError("Matrices Y0, Y0inv, and/or Y0p are undefined; either verify grid_name,"
+                               "grid_name_out, and save_dest, or call sph_compute_matrices()"
+                               "before sph_wave()!")
+        labeled = containers.is_labeled(A)
+        name = (getattr(A, "name", None) if labeled else None) or "{unnamed variable}"
+        vals = A.values if labeled else A
+        if vals.shape[0] != self.N or (labeled and tuple(A.dims)[0] != self.ncoldim):
+            raise RuntimeError("(sph_wave() Expected the first (leftmost) dimension of variable {} to be {} of length {}"
+                               .format(name, self.ncoldim, self.N))
+        is_torch = isinstance(vals, torch.Tensor)
+        t = vals if is_torch else torch.as_tensor(np.ascontiguousarray(vals))
+        in_dtype = t.dtype
+        if t.dtype not in (torch.float64, torch.float32):
+            t = t.to(torch.float64)
+        if m not in self._waves:
+            self._waves[m] = waves.WaveState(self._plan, self._lon, (m,))
+        parts = self._waves[m].project(t.to(self._plan.device), m)
+        if self._waves[m].status():
+            raise RuntimeError("Variable {} has nans! Spectral zonal averager cannot handle nans; "
+                               "please replace or remove them".format(name))
+        parts = parts.to(in_dtype) if in_dtype.is_floating_point else parts
+        outs = []
+        for what, p in zip(("cos", "sin"), parts):
+            out_vals = p.to(vals.device) if is_torch else p.cpu().numpy()
+            if labeled:
+                kind = "xarray" if containers.is_xarray(A) else "labeled"
+                coords = {k: v for k, v in dict(getattr(A, "coords", {}) or {}).items() if k != self.ncoldim}
+                coords["lat"] = self.lat_out
+                attrs = dict(DEFAULT_LAT_ATTRS)
+                attrs["long_name"] = "{} part of zonal wavenumber {} of {}".format(what, m, name)
+                out_vals = containers.make_like(kind, out_vals, ("lat",) + tuple(A.dims)[1:], coords, name, attrs)
+            outs.append(out_vals)
+        return tuple(outs)
 
     def sph_zonal_mean_native(self, A):          # sph_zonal_mean.py:285-290
         return self._sph_zonal_mean_generic(A, True)

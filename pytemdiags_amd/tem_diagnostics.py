@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib, containers, layout
 from . import climatology as clim
+from . import waves as wv
 from .constants import P0, Om
 from .sph_zonal_mean import sph_zonal_averager
 
@@ -43,7 +44,12 @@ class TEMDiagnostics:
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
                  lat_bins=None, climatology=False, tracer_mask=None, min_time_coverage=None, time_groups=None,
-                 time_weights=None, min_group_coverage=None):
+                 time_weights=None, min_group_coverage=None, lon=None, wavenumbers=None):
+        # ---- zonal wavenumbers (not in the reference; waves.py): checked before anything touches the device ----
+        self._waves, self._wave_args = None, None
+        if wavenumbers is not None:
+            self._wave_args = wv.check_arguments(wavenumbers, lon, len(lat_native), L, missing=missing, lat_bins=lat_bins,
+                                                 time_block=time_block, climatology=climatology)
         # ---- time-mean TEM (not in the reference; climatology.py): checked before anything touches the device ----
         self.min_group_coverage = clim.check_group_coverage(min_group_coverage, climatology, missing, time_groups,
                                                             time_weights, min_time_coverage)
@@ -129,6 +135,16 @@ class TEMDiagnostics:
         if self._clim is not None:
             self._climatology = self._clim.finish(self._zon)
             self._clim = None
+        if self._wave_args is not None:     # the plan is still set for the ordinary run, whose zonal means the sets share
+            self._waves = wv.build(self, plan, self._wave_args[1], self._wave_args[0], self._dev_fields, self._zon)
+
+    @property
+    def waves(self):
+        """``wavenumbers=(m, ...)`` with ``lon=``: the wave-m result sets, ``waves.TEMWaves`` (``tem.waves[m]``,
+        ``tem.waves.residual``, ``tem.waves.wavenumbers``, ``tem.waves.workspace_bytes``)."""
+        if self._waves is None:
+            raise RuntimeError("waves is not available: build the object with lon= and wavenumbers=")
+        return self._waves
 
     @property
     def climatology(self):
@@ -323,6 +339,10 @@ class TEMDiagnostics:
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (kw["missing"],))
         cls._check_tracer_mask(kw.get("tracer_mask"), kw.get("missing", "raise"), q)
         cls._check_lat_bins(kw.get("lat_bins"), kw.get("missing", "raise"))
+        if kw.get("wavenumbers") is not None:
+            wv.check_arguments(kw["wavenumbers"], kw.get("lon"), len(lat_native), kw.get("L", 50), missing=kw.get("missing", "raise"),
+                               lat_bins=kw.get("lat_bins"), time_block=kw.get("time_block"),
+                               climatology=kw.get("climatology", False))
         mgc = clim.check_group_coverage(kw.get("min_group_coverage"), kw.get("climatology", False), kw.get("missing", "raise"),
                                         kw.get("time_groups"), kw.get("time_weights"), kw.get("min_time_coverage"))
         clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"), kw.get("min_time_coverage"), mgc)
