@@ -126,15 +126,25 @@ inline int wave_check_args(int L, int64_t ncol, const double* lon_deg, int nm, c
 }
 
 // Cholesky factor of the symmetric matrix G [n][n] (row-major; the lower triangle is read): G = F F^T, F lower
-// triangular, row-major in `F`.  0, or 1 + the first pivot that is not positive (G is not positive definite).
+// triangular, row-major in `F`.  0, or 1 + the first pivot that is refused.  The rank rule: a pivot is refused when it is
+// at or below n 2^-52 max_j G[j][j] (or not finite).  A pivot that small lies inside the rounding of the Gram sums
+// themselves, so its sign and size are noise: accepting it returns noise times its reciprocal as coefficients.  The
+// measure is the LARGEST diagonal entry, not the pivot's own: a column the grid does not resolve (sin(m lon) at the
+// Nyquist wavenumber of a lat-lon grid, 1e-16 everywhere) is orthogonal to the others, so its pivot is as large as its
+// own diagonal entry, 1e-29 of the others.  The rule is relative: G times any positive factor is treated as G.  (With no
+// positive diagonal entry the bound is 0 and the rule is "not positive".)
 inline int wave_cholesky(const double* G, int n, std::vector<double>& F) {
   F.assign((size_t)n * n, 0.0);
+  double dmax = 0.0;
+  for (int j = 0; j < n; ++j)
+    if (G[(size_t)j * n + j] > dmax) dmax = G[(size_t)j * n + j];
+  const double least = (double)n * 0x1p-52 * dmax;
   for (int i = 0; i < n; ++i)
     for (int j = 0; j <= i; ++j) {
       double s = G[(size_t)i * n + j];
       for (int k = 0; k < j; ++k) s -= F[(size_t)i * n + k] * F[(size_t)j * n + k];
       if (i == j) {
-        if (!(s > 0.0) || !std::isfinite(s)) return 1 + i;
+        if (!(s > least) || !std::isfinite(s)) return 1 + i;
         F[(size_t)i * n + i] = std::sqrt(s);
       } else {
         F[(size_t)i * n + j] = s / F[(size_t)j * n + j];

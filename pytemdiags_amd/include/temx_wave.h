@@ -55,6 +55,11 @@ int temxk_version(void); /* 100 */
  * longitude that is not finite.  TEMX_EUNSUPPORTED: Kc = 2 (L + 1 - m) > TEMXK_KC_MAX, and a plan in weights mode, in
  * missing-value mode, on latitude bins or finalised with a Gram matrix from outside (an ncol-sharded job).
  * TEMX_ERANK, with m in the message: Gm is not positive definite (the grid does not resolve wavenumber m at degree L).
+ * The rule: a pivot of the Cholesky factorisation of Gm [Kc][Kc] at or below Kc 2^-52 max_j Gm[j][j] is refused -- it
+ * lies inside the rounding of the sums that make Gm.  It is relative to the LARGEST diagonal entry: on a lat-lon grid of
+ * nlon longitudes sin(m lon) at m = nlon / 2 is 1e-16 in every column, orthogonal to the cos half, and its pivots are
+ * 1e-29 of the others (refused), while at m = nlon / 2 - 1 the smallest pivot is 0.9 of the largest diagonal entry.  No
+ * state is made (*out stays null) and the plan is as before the call.
  * The call runs the plan's own temx_zonal_mean once per wavenumber on Kc columns (the deflation): the plan's operator
  * workspace may grow to that width; no result of the plan and none of its TEM state changes. */
 int temxk_wave_create(temxk_wave** out, temx_plan* plan, const double* lon_deg_host /* [ncol] */, int nm,

@@ -3,8 +3,10 @@
 // Prints, for m in {1, 4, 32} and L = 255, at the latitudes of `lats`, one line "P m lat_index v_m v_{m+1} ... v_L" of
 // Pbar_l^m(sin lat) (17 significant digits; tests/test_wave_host.py compares them with scipy), then checks on its own:
 // the Kc / padding arithmetic of wave_shape for every (L, m) up to L = 511, the argument checker's codes, and the
-// Cholesky factor and inverse on a small matrix.  Prints "shapes=<n> refusals=<n> cholesky=ok"; a failed check prints
-// the case and exits 1.
+// Cholesky factor and inverse on a small matrix, and the rank rule of wave_cholesky (a positive definite matrix with one
+// row and column scaled by 1e-14 is refused at that pivot; the same matrix times 1e-30 overall is accepted; an accepted
+// matrix keeps the textbook factor bit for bit).  Prints "shapes=<n> refusals=<n> cholesky=ok rank=ok"; a failed check
+// prints the case and exits 1.
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -105,9 +107,56 @@ int main() {
         for (int k = 0; k < n; ++k) s += G[(size_t)i * n + k] * Gi[(size_t)k * n + j];
         if (std::fabs(s - (i == j ? 1.0 : 0.0)) > 1e-12) return bad("G Ginv = I", i, j);
       }
+    // ---- the rank rule: a pivot at or below n 2^-52 max_j G[j][j] is refused ----
+    // the factor of an accepted matrix is that of the textbook recurrence, bit for bit (the rule only refuses)
+    auto textbook = [](const std::vector<double>& Gm, int nn) {
+      std::vector<double> T((size_t)nn * nn, 0.0);
+      for (int i = 0; i < nn; ++i)
+        for (int j = 0; j <= i; ++j) {
+          double s = Gm[(size_t)i * nn + j];
+          for (int k = 0; k < j; ++k) s -= T[(size_t)i * nn + k] * T[(size_t)j * nn + k];
+          T[(size_t)i * nn + j] = i == j ? std::sqrt(s) : s / T[(size_t)j * nn + j];
+        }
+      return T;
+    };
+    if (F != textbook(G, n)) return bad("the factor of an accepted matrix is unchanged", n, 0);
+    // the same matrix times 1e-30 overall: accepted (the rule is relative), and its inverse is still one
+    std::vector<double> Gs(G);
+    for (double& v : Gs) v *= 1e-30;
+    if (wave_cholesky(Gs.data(), n, F) != 0) return bad("a small but well-conditioned matrix is accepted", n, 0);
+    if (F != textbook(Gs, n)) return bad("the factor of the scaled matrix is the textbook one", n, 0);
+    wave_inverse_from_factor(F, n, Gi.data());
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) {
+        double s = 0.0;
+        for (int k = 0; k < n; ++k) s += Gs[(size_t)i * n + k] * Gi[(size_t)k * n + j];
+        if (std::fabs(s - (i == j ? 1.0 : 0.0)) > 1e-12) return bad("scaled G Ginv = I", i, j);
+      }
+    // one row and column scaled by 1e-14 (a basis column of 1e-14, its Gram entry 1e-28): still positive definite in
+    // exact arithmetic, with a positive pivot -- refused, at that pivot, wherever it stands
+    for (int r = 0; r < n; ++r) {
+      std::vector<double> Gr(G);
+      for (int k = 0; k < n; ++k) {
+        Gr[(size_t)r * n + k] *= 1e-14;
+        Gr[(size_t)k * n + r] *= 1e-14;
+      }
+      const std::vector<double> T = textbook(Gr, n);
+      if (!(T[(size_t)r * n + r] > 0.0)) return bad("the scaled pivot is positive: the old rule accepted it", n, r);
+      if (wave_cholesky(Gr.data(), n, F) != 1 + r) return bad("a pivot inside the rounding of the sums is refused, and named", n, r);
+    }
+    // just above the bound is accepted, at the bound is refused: diag(1, t), bound 2 * 2^-52
+    {
+      const double at = 2 * 0x1p-52;
+      const double up[4] = {1.0, 0.0, 0.0, at * (1 + 0x1p-52)}, on[4] = {1.0, 0.0, 0.0, at};
+      if (wave_cholesky(up, 2, F) != 0) return bad("a pivot above the bound is accepted", 2, 1);
+      if (wave_cholesky(on, 2, F) != 2) return bad("a pivot at the bound is refused", 2, 1);
+    }
     G[(size_t)3 * n + 3] = -1.0;
     if (wave_cholesky(G.data(), n, F) != 4) return bad("the failing pivot is named", n, 3);
+    // no positive diagonal entry: the bound is 0, the first pivot fails
+    const double neg[4] = {-1.0, 0.0, 0.0, -2.0}, zero[1] = {0.0};
+    if (wave_cholesky(neg, 2, F) != 1 || wave_cholesky(zero, 1, F) != 1) return bad("no positive diagonal", 2, 0);
   }
-  std::printf("shapes=%lld refusals=%d cholesky=ok\n", shapes, refusals);
+  std::printf("shapes=%lld refusals=%d cholesky=ok rank=ok\n", shapes, refusals);
   return 0;
 }

@@ -2,7 +2,8 @@
 the refusals of the front end that are decided before any device call, and the host tables of the fit
 (pytemdiags_amd/csrc/wave_tables.hpp, which needs no HIP) on their own under AddressSanitizer + UBSan: the normalised
 recurrence of ``Pbar_l^m`` against ``scipy.special.lpmv``, the Kc / padding arithmetic, the argument checker's codes and
-the Cholesky factor.  Needs no GPU.
+the Cholesky factor with its rank rule (a pivot at or below n 2^-52 of the largest diagonal entry is refused).  Needs no
+GPU.
 
 Bound of the recurrence: 1e-12 relative to the maximum of the row (one m, one latitude, l = m..255), at m in 1, 4, 32 and
 latitudes that include +-89.9 degrees and the equator."""
@@ -130,6 +131,48 @@ def test_wave_tables_shapes_checker_and_cholesky(tmp_path_factory):
     m = re.search(r"shapes=(\d+) refusals=(\d+) cholesky=ok", _tables_output(tmp_path_factory))
     assert m
     assert int(m.group(1)) == 511 * 512 // 2 and int(m.group(2)) == 10
+
+
+def test_wave_tables_rank_rule(tmp_path_factory):
+    """``wave_cholesky`` refuses a pivot at or below n 2^-52 max_j G[j][j]: the program's own checks (a positive definite
+    5 x 5 matrix with row and column r scaled by 1e-14 is refused at pivot r, for every r, although the textbook
+    recurrence finds that pivot positive; the same matrix times 1e-30 overall is accepted and inverted; the factor of
+    every accepted matrix is the textbook one bit for bit; diag(1, t) is refused at t = 2 * 2^-52 and accepted one ulp
+    above), and the rule restated here on the Nyquist basis of the 12 x 16 grid, whose numbers the rule was made for."""
+    out = _tables_output(tmp_path_factory)
+    assert "FAILED" not in out and re.search(r"cholesky=ok rank=ok\s*$", out)
+    src = open(os.path.join(ROOT, "pytemdiags_amd", "csrc", "wave_tables.hpp")).read()
+    assert "(double)n * 0x1p-52 * dmax" in src and "if (!(s > least) || !std::isfinite(s)) return 1 + i;" in src
+    # the numbers of the rule, in numpy: smallest pivot over largest diagonal entry of Ym^T Ym
+    scipy_special = pytest.importorskip("scipy.special")
+    from pytemdiags_amd import synth
+
+    def ratio(nlat, nlon, L, mm):
+        lat, lon = synth.latlon_grid(nlat, nlon)
+        l = np.arange(mm, L + 1)
+        norm = np.sqrt(2.0) * np.sqrt((2 * l + 1) / (4 * np.pi)
+                                      * np.exp(scipy_special.gammaln(l - mm + 1) - scipy_special.gammaln(l + mm + 1)))
+        P = norm[None, :] * scipy_special.lpmv(mm, l[None, :], np.sin(np.deg2rad(lat))[:, None])
+        lam = np.deg2rad(lon)[:, None]
+        Y = np.concatenate([P * np.cos(mm * lam), P * np.sin(mm * lam)], axis=1)
+        G = Y.T @ Y
+        n, F = G.shape[0], np.zeros_like(G)
+        piv = []
+        for i in range(n):
+            for j in range(i + 1):
+                s = G[i, j] - F[i, :j] @ F[j, :j]
+                if i == j:
+                    piv.append(s)
+                    F[i, i] = np.sqrt(abs(s))
+                else:
+                    F[i, j] = s / F[j, j]
+        return min(piv) / G.diagonal().max(), n * 2.0 ** -52
+
+    for nlat, nlon, L, mm, refused in ((12, 16, 8, 8, True), (12, 16, 8, 7, False), (32, 48, 24, 24, True),
+                                       (32, 48, 24, 23, False), (24, 48, 24, 1, False)):
+        r, bound = ratio(nlat, nlon, L, mm)
+        print("%d x %d L = %d m = %d: smallest pivot / largest diagonal %.2e (bound %.2e)" % (nlat, nlon, L, mm, r, bound))
+        assert (r <= bound) == refused and (r < 1e-12 * bound if refused else r > 0.2), (nlat, nlon, L, mm, r)
 
 
 @pytest.mark.parametrize("j", range(len(LATS)), ids=["lat%+.1f" % a for a in LATS])
