@@ -19,10 +19,9 @@
 // Tile scheme, operand layouts and staging are those of kernels.hpp.
 #pragma once
 #include "kernels.hpp"
+#include "shared_defs.hpp"   // SYM_PROJ_CH, the pair-groups per chunk of the paired project sweep
 
 namespace temx {
-
-constexpr int SYM_PROJ_CH = 3;   // pair-groups per chunk of the paired project sweep
 
 template <int KMAX>
 __global__ void sym_basis_kernel(const double* __restrict__ x, const int* __restrict__ rowN, int64_t npair,

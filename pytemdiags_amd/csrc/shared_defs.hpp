@@ -1,5 +1,5 @@
 // shared_defs.hpp -- constants and plain structs that the host headers (class_tables.hpp, side_tables.hpp,
-// launch_shapes.hpp) and the kernels both use.  No HIP: it compiles with any C++17 compiler.
+// launch_shapes.hpp, tem_layout.hpp) and the kernels both use.  No HIP: it compiles with any C++17 compiler.
 #ifndef TEMX_SHARED_DEFS_HPP
 #define TEMX_SHARED_DEFS_HPP
 
@@ -10,6 +10,9 @@ constexpr int CLS_MB = 4;                     // member rows per class and batch
 constexpr int CLS_PADB = 10;                  // batches of padding behind crow (index loads run up to PD + 1 ahead)
 constexpr int CLS_HASPAD_BIT = 1 << 27;       // the batch has at least one padding entry (set in all its entries)
 constexpr int CLS_SOUTH = 1, CLS_FIRST = 2, CLS_LAST = 4;   // flags, stored at bit 28
+
+// ---- mirror-paired sweeps (kernels_sym.hpp; cut by tem_layout.hpp) ------------------------------------------------
+constexpr int SYM_PROJ_CH = 3;                // pair-groups per chunk of the paired project sweep
 
 // ---- vertical interpolation (kernels_vert.hpp; shape chosen by launch_shapes.hpp, vert_slab_shape) ---------------
 constexpr int VERT_THREADS = 256;

@@ -1,5 +1,7 @@
 // temx.hip -- host side of libtemx.so: plan, workspace, launch logic and the C ABI of
 // include/temx.h.  gfx950 only.  Build: see csrc/Makefile (hipcc --offload-arch=gfx950).
+// What can be decided without a device is not here: the tables and launch shapes of a plan, the argument rules, the
+// dispatch lists, and the form, cuts and buffer sizes of the TEM configuration (tem_layout.hpp) are HIP-free headers.
 #include "../../include/temx.h"
 #include "../../include/temx_vert.h"
 #include "../../include/temx_layout.h"
@@ -56,6 +58,7 @@
 #include "host_math.hpp"
 #include "launch_shapes.hpp"
 #include "mgclim_shapes.hpp"
+#include "tem_layout.hpp"
 #include "wave_tables.hpp"
 
 using namespace temx;
@@ -396,34 +399,11 @@ static void time_end(temx_plan* pl, int which, hipStream_t st, TimedLaunch& tl) 
 // ------------------------------------------------------------------------------------------------
 // sweep-1 configurations (fields per wave, X ring depth, waves per SIMD).  Measured on
 // ne120x72x30: 2 fields/wave with 2- or 3-deep rings at 3 waves/SIMD were within +-3 % of this.
-struct ProjCfgC { static constexpr int NFW = 4, PD = 1, WPS = 2; };   // default: quads of d-tiles
-struct ProjCfgE { static constexpr int NFW = 1, PD = 2, WPS = 3; };   // small ragged D: one d-tile per workgroup
-struct ProjCfg1 { static constexpr int NFW = 1, PD = 2, WPS = 2; };   // single-field operator API / Gram
-
-// d-tiles per workgroup that waste the fewest wave slots on a ragged last workgroup
-static int pick_dpw(int ndt, int maxdpw) {
-  int best = maxdpw;
-  double bw = 1e9;
-  for (int d = maxdpw; d >= 1; d >>= 1) {
-    const double w = (double)(((ndt + d - 1) / d) * d) / ndt;
-    if (w < bw - 0.05) {
-      bw = w;
-      best = d;
-    }
-  }
-  return best;
-}
-static int proj_dpw(int NF, int ndt) {
-  if (NF == 1) return 4;
-  return pick_dpw(ndt, 4) == 1 ? 1 : 4;     // small ragged D: config E (1 field per wave)
-}
-static int proj_wps(int NF, int dpw) {
-  if (NF == 1) return ProjCfg1::WPS;
-  return dpw == 1 ? ProjCfgE::WPS : ProjCfgC::WPS;
-}
-
-constexpr int SYM_PROJ_E_WPS = 3;
-struct ProjCfg3 { static constexpr int NFW = 3, PD = 1, WPS = 2; };   // the 3 eddy products (large-L path)
+// (the waves per SIMD enter the cuts: tem_layout.hpp, with pick_dpw / proj_dpw / proj_wps)
+struct ProjCfgC { static constexpr int NFW = 4, PD = 1, WPS = PROJ_C_WPS; };   // default: quads of d-tiles
+struct ProjCfgE { static constexpr int NFW = 1, PD = 2, WPS = PROJ_E_WPS; };   // small ragged D: one d-tile per workgroup
+struct ProjCfg1 { static constexpr int NFW = 1, PD = 2, WPS = PROJ_1_WPS; };   // single-field operator API / Gram
+struct ProjCfg3 { static constexpr int NFW = 3, PD = 1, WPS = PROJ_3_WPS; };   // the 3 eddy products (large-L path)
 
 template <int NF>
 static int launch_project(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype, int64_t D,
@@ -616,20 +596,12 @@ static int os_cuts_dev(temx_plan* pl, bool sub, int nsub, const int2** out) {
   return cached_cuts(pl->csplits_s, pl->sgbatch0, pl->sgroups, pl->sbatches, nsub, true, out);
 }
 
-#ifndef TEMX_CLS_E_WPS
-#define TEMX_CLS_E_WPS 3
-#endif
+// (TEMX_CLS_E_WPS, TEMX_CLS_OP_WPS and TEMX_CLS_MINCHUNK enter the cuts: tem_layout.hpp)
 #ifndef TEMX_CLS_E_PD
 #define TEMX_CLS_E_PD 2
 #endif
-#ifndef TEMX_CLS_OP_WPS
-#define TEMX_CLS_OP_WPS 1
-#endif
 #ifndef TEMX_CLS_OP_PD
 #define TEMX_CLS_OP_PD 3
-#endif
-#ifndef TEMX_CLS_MINCHUNK
-#define TEMX_CLS_MINCHUNK 1
 #endif
 #ifndef TEMX_CLS_OP_PD_F32
 #define TEMX_CLS_OP_PD_F32 6
@@ -640,7 +612,7 @@ static int os_cuts_dev(temx_plan* pl, bool sub, int nsub, const int2** out) {
 #ifndef TEMX_CLS_Q_PD_F32
 #define TEMX_CLS_Q_PD_F32 2
 #endif
-constexpr int CLS_PROJ_E_WPS = TEMX_CLS_E_WPS, CLS_PROJ_E_PD = TEMX_CLS_E_PD;   // one field per wave
+constexpr int CLS_PROJ_E_PD = TEMX_CLS_E_PD;   // one field per wave (CLS_PROJ_E_WPS: tem_layout.hpp)
 // X batches a wave of the class project sweep holds (PD - 1 in flight).  A batch of fp32 carries half
 // the bytes of an fp64 one in half the registers, so fp32 inputs get rings twice as deep: the same
 // bytes in flight per wave.
@@ -833,6 +805,15 @@ static int launch_eddy_sym_t(temx_plan* pl, const FieldPtrs<4>& fp, const double
 // The fused second sweep reads ONE set of Y0 blocks for the reconstruction and for the projection, so it
 // serves neither K > 64 nor weights mode (projection rows scaled by 4 pi w, reconstruction rows not).
 static inline bool unfused_stage2(const temx_plan* pl) { return pl->large || pl->weighted; }
+// what tem_layout.hpp reads of a plan
+static TemDims tem_dims(const temx_plan* pl) {
+  TemDims d;
+  d.N = pl->N; d.nchunk = pl->nchunk; d.K = pl->K; d.K4 = pl->K4; d.M = pl->M; d.num_cu = pl->num_cu;
+  d.nlev = pl->nlev; d.nt = pl->nt;
+  d.unfused_stage2 = unfused_stage2(pl); d.lcls = pl->lcls; d.cls = pl->cls; d.sym = pl->sym;
+  d.cgroups = pl->cgroups; d.cbatches = pl->cbatches; d.npg = pl->npg;
+  return d;
+}
 
 static inline hipStream_t S_(void* s) { return static_cast<hipStream_t>(s); }
 static inline const Split& eddy_split(const temx_plan* pl) {
@@ -997,7 +978,7 @@ static int launch_sweep_os_t(temx_plan* pl, const FieldPtrs<4>& fp, bool sub, co
   const int2* cuts = nullptr;
   if (int rc = os_cuts_dev(pl, sub, sp.nsplit, &cuts)) return rc;
   dim3 grid(sp.grid), block(256);
-  constexpr int NBR = 2;
+  constexpr int NBR = OS_NBR;
   constexpr int PDv = sizeof(T) == 4 ? 4 : 2;       // (a 3-deep ring measured slower for the tracer kind: 8.7 vs 8.4 ms)
   constexpr int DF = TEMX_OS_DEFER;                 // projection of a finished class-group spread over the next 4 batches
   // loads of 1 row x 64 columns (sweep_osr_kernel, the default) or of 4 rows x 16 columns (TEMX_OS_MAP=tile, A/B)
@@ -1013,8 +994,7 @@ static int launch_sweep_os_t(temx_plan* pl, const FieldPtrs<4>& fp, bool sub, co
       if (tile_map) return fail(TEMX_EUNSUPPORTED, "two tracers per sweep: row-map sweeps only");
     }
     if constexpr (KIND != 3) if (tile_map) {
-      const size_t lds = ((size_t)4 * (DF ? 2 : 1) * 2 * TBXv * 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +
-                          (size_t)4 * KD::NP * 2 * TBSv * 64) * 8;
+      constexpr size_t lds = sweep_os_lds(TBSv, TBXv, KD::NF, KD::NP, KD::NPR, DF);
       return launch_lds<sweep_os_kernel<T, TBSv, TBXv, NBR, PDv, KIND, DF>>(pl->device, grid, block, lds, st, fp, pl->D,
           pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(), static_cast<const int4*>(sub ? pl->crow_s.p : pl->crow.p), cuts,
           pl->colscale.d(), rho, pl->KR, px, pp, sp.nsplit, sp.ndt);
@@ -1024,8 +1004,7 @@ static int launch_sweep_os_t(temx_plan* pl, const FieldPtrs<4>& fp, bool sub, co
         return fail(TEMX_EUNSUPPORTED, "single sweep of fp32 fields: a latitude class of this plan has %lld members on one "
                     "side, and the sweep sums a side in fp32; create the plan with TEMX_LAT_TOL_F32",
                     (long long)pl->cls_max_side);
-      const size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +
-                          (size_t)8 * (KD::NP - KD::NPR) * TBSv * 64 + (size_t)(KD::NF + KD::NP) * 512) * 8;
+      constexpr size_t lds = sweep_os2_lds(TBSv, TBXv, KD::NF, KD::NP, KD::NPR, DF);
       const int si = sub ? 1 : 0;
       return launch_lds<sweep_os2_kernel<float, TBSv, TBXv, NBR, 2, KIND>>(
           pl->device, grid, dim3(512), lds, st, fp, pl->D, pl->K, pl->KX, sub ? pl->ycx_s.d() : pl->ycx.d(),
@@ -1033,9 +1012,7 @@ static int launch_sweep_os_t(temx_plan* pl, const FieldPtrs<4>& fp, bool sub, co
           static_cast<const int*>(pl->side_gfirst[si][0].p), static_cast<const int*>(pl->side_gfirst[si][1].p),
           cuts, pl->colscale.d(), rho, pl->KR, px, pp, sp.nsplit, sp.ndt);
     }
-    // Y blocks x 2 | counts | reference operands | product accumulators | exchange | the flag form's two counters
-    constexpr size_t lds = ((size_t)2 * 2 * TBXv * 16 + 16 + (size_t)4 * KD::NF * 2 * NBR * 64 +
-                            (size_t)4 * (KD::NP - KD::NPR) * 2 * TBSv * 64 + (size_t)2 * (KD::NF + KD::NP) * 256 + 2) * 8;
+    constexpr size_t lds = sweep_osr_lds(TBSv, TBXv, KD::NF, KD::NP, KD::NPR, DF);
     static_assert(lds <= 163840, "the single sweep's workgroup fits the LDS of a compute unit");
     auto go = [&](auto handoff) {     // 0: two workgroup barriers per group, 1: LDS flags
       return launch_lds<sweep_osr_kernel<double, TBSv, TBXv, NBR, 2, KIND, decltype(handoff)::value>>(pl->device, grid,
@@ -1056,9 +1033,7 @@ static int launch_sweep_os(temx_plan* pl, const FieldPtrs<4>& fp, int dtype, boo
 }
 
 static bool os_supported(const temx_plan* pl) {
-  if (!pl->cls || pl->large || pl->weighted || !pl->qbasis || pl->h_crow.empty()) return false;
-  const int tbx = (pl->L + 1 + 3) / 4;          // blocks of 4 even harmonics up to degree 2L
-  return (pl->TBS == 7 && tbx <= 13) || (pl->TBS == 4 && tbx <= 8) || (pl->TBS == 2 && tbx <= 4);
+  return os_supported(pl->cls, pl->large, pl->weighted, pl->qbasis, !pl->h_crow.empty(), pl->TBS, pl->L);
 }
 
 // the single-sweep forms run for both input types (fp32 inputs take the two-waves-per-SIMD sweep);
@@ -1220,14 +1195,14 @@ static int tracer_ws(temx_plan* pl);
 // projected to degree 2L, q v and q omega to degree L.  The same three steps as the TEM run; for nq tracers:
 // Asq[nq][KR][D], projq = nq KX + 2 nq K rows (the q's, then q1 v, q1 omega, q2 v, q2 omega).
 static int tracer_os_ws(temx_plan* pl, int nq) {
-  const int64_t D = pl->D;
+  const TracerOsWs w = tracer_os_ws_layout(tem_dims(pl), nq, pl->KX, pl->KR, pl->NQ);
   int rc;
   if ((rc = tracer_ws(pl))) return rc;
-  if ((rc = pl->Axq.ensure((size_t)nq * (pl->KX + 2 * pl->K + pl->KR) * D * 8))) return rc;   // projections, then the pre-pass sums
-  if ((rc = pl->osAtq.ensure((size_t)nq * pl->NQ * D * 8))) return rc;
-  if ((rc = pl->osAbq.ensure((size_t)nq * pl->NQ * D * 8))) return rc;
-  if ((rc = pl->Bqp.ensure((size_t)nq * 3 * pl->K * D * 8))) return rc;                       // raw sums of the q's, then of the products
-  return pl->rho_t.ensure((size_t)4 * pl->KR * D * 8);
+  if ((rc = pl->Axq.ensure(w.Axq))) return rc;
+  if ((rc = pl->osAtq.ensure(w.osAtq))) return rc;
+  if ((rc = pl->osAbq.ensure(w.osAbq))) return rc;
+  if ((rc = pl->Bqp.ensure(w.Bqp))) return rc;
+  return pl->rho_t.ensure(w.rho_t);
 }
 
 // fp: (q, v, omega, -) for one tracer, (q1, q2, v, omega) for two
@@ -1393,7 +1368,7 @@ static int launch_miss_project(temx_plan* pl, const FieldPtrs<NF>& fp, int dtype
   return by_dtype(dtype, [&](auto t) {
     const Split sp = choose_split(D, pl->nchunk, pl->num_cu, 4);
     const int64_t R = (int64_t)NF * pl->K + pl->NE;
-    if (int rc = pl->partial.ensure(std::max((size_t)sp.nsplit * R * D * 8, pl->partial.bytes))) return rc;
+    if (int rc = pl->partial.ensure((size_t)sp.nsplit * R * D * 8)) return rc;
     const int rc = dispatch(TBValues{}, pl->TB, [&](auto tb) {
       constexpr int TBv = decltype(tb)::value;
       return launch<miss_project_kernel<typename decltype(t)::type, NF, TBv, 2 * TBv>>(
@@ -1463,7 +1438,7 @@ static int launch_miss_tracer_project(temx_plan* pl, const FieldPtrs<3>& fp, int
   return by_dtype(dtype, [&](auto t) {
     const Split sp = choose_split(D, pl->nchunk, 2 * pl->num_cu, 4);
     const int64_t R = (int64_t)pl->K + pl->NE;
-    if (int rc = pl->partial.ensure(std::max((size_t)sp.nsplit * R * D * 8, pl->partial.bytes))) return rc;
+    if (int rc = pl->partial.ensure((size_t)sp.nsplit * R * D * 8)) return rc;
     const int rc = dispatch(TBValues{}, pl->TB, [&](auto tb) {
       constexpr int TBv = decltype(tb)::value;
       using T = typename decltype(t)::type;
@@ -2486,26 +2461,9 @@ int temx_zonal_mean(temx_plan* pl, const void* A, int dtype, int64_t D, double* 
 } TEMX_CATCH
 
 // ---- path selection: temx_plan_configure sets the options, the TEMX_* environment variables override them ------
-struct FormChoice {
-  bool two_pass;      // the class path in its two-pass form
-  bool force_op;      // the one-pass form wherever it is possible (lifts the size threshold)
-  int os;             // single sweep: 0 never, 1 wherever the instantiations exist, -1 automatic
-};
+// (the rules: tem_layout.hpp, form_choice)
 static FormChoice form_choice(const temx_plan* pl) {
-  FormChoice c{false, false, -1};
-  if (bin_mode(pl)) return FormChoice{true, false, 0};   // the binned form ignores the overrides; what runs next to it
-                                                         // (eddies, tracers) is the plan's two-pass form
-  switch (pl->opt_form) {
-    case TEMX_FORM_TWO_PASS: c.two_pass = true; c.os = 0; break;
-    case TEMX_FORM_CLASS_SUMS: c.force_op = true; c.os = 0; break;
-    case TEMX_FORM_SINGLE_SWEEP: c.force_op = true; c.os = 1; break;
-    case TEMX_FORM_NO_SINGLE_SWEEP: c.os = 0; break;
-    default: break;
-  }
-  if (const char* e = getenv("TEMX_TWO_PASS")) c.two_pass = e[0] == '1';
-  if (const char* e = getenv("TEMX_ONE_PASS")) c.force_op = c.force_op || e[0] == '1';
-  if (const char* e = getenv("TEMX_SINGLE_SWEEP")) c.os = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : c.os);
-  return c;
+  return form_choice(pl->opt_form, bin_mode(pl), getenv("TEMX_TWO_PASS"), getenv("TEMX_ONE_PASS"), getenv("TEMX_SINGLE_SWEEP"));
 }
 // 1: loads of 4 rows x 16 columns (the MFMA tile), 0: loads of 1 row x 64 columns
 static bool tile_map(int opt, const char* env) {
@@ -2606,6 +2564,102 @@ int temx_plan_option(const temx_plan* pl, int option) try {
 } TEMX_CATCH
 
 // ---- TEM pipeline --------------------------------------------------------------------------------
+// temx_plan_set_tem, path by path: tem_layout.hpp decides, these allocate, fill and upload the work cuts (now, not at
+// the first launch: launches must stay legal inside a stream capture).
+static bool mem_free(size_t* fr) {
+  size_t tot = 0;
+  return hipMemGetInfo(fr, &tot) == hipSuccess;
+}
+
+// large-L class path: class sums first (kernels_cls.hpp) if both of their streams fit, the sliced two-pass sweeps if not
+static int set_tem_large_cls(temx_plan* pl, const TemDims& d, const FormChoice& fc) {
+  const LargeClsLayout l = tem_large_cls_layout(d, fc);
+  size_t fr = 0;
+  if (!(l.eligible && mem_free(&fr) && fits(l.csum, pl->csum.bytes, fr, l.pbuf) &&
+        alloc_write_stream(pl->csum, l.csum) == TEMX_OK && pl->pbuf.ensure(l.pbuf) == TEMX_OK))
+    return TEMX_OK;
+  int rc;
+  HIPCHK(hipMemset(pl->csum.p, 0, pl->csum.bytes));
+  HIPCHK(hipMemset(pl->pbuf.p, 0, pl->pbuf.bytes));
+  pl->sp_cproj4 = l.sp_cproj4;
+  pl->sp_cflux = l.sp_cflux;
+  pl->sp_lflux = l.sp_lflux;
+  if ((rc = pl->partial.ensure(l.partial))) return rc;
+  if ((rc = pl->Bs.ensure(l.Bs))) return rc;
+  const int2* cuts_unused = nullptr;
+  if ((rc = class_cuts_dev(pl, pl->sp_cproj4.nsplit, &cuts_unused, true))) return rc;
+  pl->lone = true;
+  return TEMX_OK;
+}
+
+// single sweep (no class-sum stream): its tables, then its buffers.  Too few distinct latitudes in the subsample
+// (TEMX_ERANK) leave the plan on the class-sum form.
+static int set_tem_single_sweep(temx_plan* pl, const TemDims& d) {
+  int rc = build_os_tables(pl);
+  if (rc == TEMX_ERANK) return TEMX_OK;
+  if (rc) return rc;
+  const SweepLayout s = tem_sweep_layout(d, pl->KX, pl->KR, pl->NQ, pl->sbatches);
+  pl->sp_os = s.sp_os;
+  pl->sp_os_s = s.sp_os_s;
+  if ((rc = pl->partial.ensure(s.partial))) return rc;
+  if ((rc = pl->Ax.ensure(s.Ax))) return rc;
+  if ((rc = pl->Axs.ensure(s.Axs))) return rc;
+  if ((rc = pl->osAt.ensure(s.osAt))) return rc;
+  if ((rc = pl->osAb.ensure(s.osAb))) return rc;
+  if ((rc = pl->rho.ensure(s.rho))) return rc;
+  if ((rc = pl->rho0.ensure(s.rho0))) return rc;
+  HIPCHK(hipMemset(pl->rho0.p, 0, pl->rho0.bytes));
+  const int2* cu = nullptr;
+  if ((rc = os_cuts_dev(pl, false, pl->sp_os.nsplit, &cu))) return rc;
+  if ((rc = os_cuts_dev(pl, true, pl->sp_os_s.nsplit, &cu))) return rc;
+  pl->os_on = true;
+  return TEMX_OK;
+}
+
+// class path: the two-pass cuts; the one-pass form where it is wanted and the class sums find room (no memory: the
+// two-pass form stays); the single sweep where that is wanted on top
+static int set_tem_cls(temx_plan* pl, const TemDims& d, const FormChoice& fc) {
+  int rc;
+  const ClsLayout c = tem_cls_layout(d, fc);
+  pl->sp_cproj4 = c.sp_cproj4;
+  pl->sp_cproj1 = c.sp_cproj1;
+  pl->sp_ceddy = c.sp_ceddy;
+  if ((rc = pl->partial.ensure(c.partial))) return rc;
+  bool have = c.want_onepass && pl->csum.bytes >= c.csum;
+  size_t fr = 0;
+  if (c.want_onepass && !have && mem_free(&fr) && fits(c.csum, pl->csum.bytes, fr) &&
+      alloc_write_stream(pl->csum, c.csum) == TEMX_OK) {
+    // lanes beyond a ragged last d-tile are never written but are read (and ignored) by the flux kernel
+    HIPCHK(hipMemset(pl->csum.p, 0, pl->csum.bytes));
+    have = true;
+  }
+  if (have) {
+    const OnePassLayout o = tem_onepass_layout(d, fc, os_supported(pl), pl->opt_single_sweep_min_groups);
+    pl->onepass = true;
+    pl->sp_cproj4 = o.sp_cproj4;
+    pl->sp_cflux = o.sp_cflux;
+    pl->sp_copw = o.sp_copw;
+    if ((rc = pl->partial.ensure(o.partial))) return rc;
+    if ((rc = pl->Pq.ensure(o.Pq))) return rc;
+    if (o.want_os && (rc = set_tem_single_sweep(pl, d))) return rc;
+  }
+  const int2* cuts_unused = nullptr;
+  if (pl->onepass && (rc = class_cuts_dev(pl, pl->sp_cproj4.nsplit, &cuts_unused, true))) return rc;
+  if (pl->onepass && (rc = class_cuts_dev(pl, pl->sp_copw.nsplit * 4, &cuts_unused, true))) return rc;
+  for (int nsub : {pl->sp_cproj4.nsplit, pl->sp_cproj1.nsplit, pl->sp_ceddy.nsplit * (8 / d.edpw())})
+    if ((rc = class_cuts_dev(pl, nsub, &cuts_unused))) return rc;
+  return TEMX_OK;
+}
+
+// mirror-paired path
+static int set_tem_sym(temx_plan* pl, const TemDims& d) {
+  const SymLayout s = tem_sym_layout(d);
+  pl->sp_sproj4 = s.sp_sproj4;
+  pl->sp_sproj1 = s.sp_sproj1;
+  pl->sp_seddy = s.sp_seddy;
+  return pl->partial.ensure(s.partial);
+}
+
 int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_host, double p0) try {
   if (!pl || !p_pa_host) return fail(TEMX_EINVAL, "null argument");
   if (nlev < 2 || nt < 1) return fail(TEMX_EINVAL, "need nlev >= 2 and nt >= 1");
@@ -2635,8 +2689,6 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
   pl->tnt = nt;
   pl->tt0 = 0;
   pl->p0 = p0;
-  const int M = pl->M;
-  const int64_t D = pl->D;
   int rc;
   const TemTables tt = tem_tables(p, nt, p0, pl->lat_out_deg);
   if ((rc = upload(pl->p, p))) return rc;
@@ -2646,151 +2698,23 @@ int temx_plan_set_tem(temx_plan* pl, int nlev, int64_t nt, const double* p_pa_ho
   if ((rc = upload(pl->fcor, tt.fcor))) return rc;
   if ((rc = upload(pl->colscale, tt.colscale))) return rc;
 
-  const int ndt_ = (int)((D + 15) / 16);
-  const int pdpw = proj_dpw(4, ndt_);
-  pl->sp_proj4 = choose_split(D, pl->nchunk, proj_wps(4, pdpw) * pl->num_cu, pdpw);
-  // eddy sweep: one 8-wave workgroup per CU (LDS slabs) owning dpw d-tiles; the 8/dpw waves on a
-  // d-tile split its chunk range -> 8/dpw partial slabs per split
-  const int edpw = pick_dpw(ndt_, 4);
-  pl->sp_eddy = choose_split(D, pl->nchunk / (8 / edpw), pl->num_cu, edpw);
-  const size_t need =
-      (size_t)std::max(pl->sp_proj4.nsplit * 4, pl->sp_eddy.nsplit * (8 / edpw) * 3) * pl->K * D * 8;
-  if ((rc = pl->partial.ensure(need))) return rc;
-  if ((rc = pl->B4.ensure((size_t)4 * pl->K * D * 8))) return rc;
-  if ((rc = pl->B3.ensure((size_t)3 * pl->K * D * 8))) return rc;
-  if ((rc = pl->C4.ensure((size_t)4 * pl->K4 * D * 8))) return rc;
-  if ((rc = pl->zb.ensure((size_t)8 * M * D * 8))) return rc;
-  pl->sp_proj1 = choose_split(D, pl->nchunk, 2 * pl->num_cu);
-  if (unfused_stage2(pl)) {   // products are projected three at a time, 64 harmonics per pass
-    const size_t need3 = (size_t)pl->sp_proj1.nsplit * 3 * 64 * D * 8;
-    if ((rc = pl->partial.ensure(std::max(need3, pl->partial.bytes)))) return rc;
-  }
-  pl->lone = false;
-  pl->xb_valid = false;
-  pl->op_valid = false;      // class sums of an earlier configuration are void
-  if (pl->lcls) {    // large-L class path: class sums first (kernels_cls.hpp), if they fit
-    const size_t need_cs = (size_t)pl->cgroups * ndt_ * 14 * 64 * 8, need_pb = (size_t)pl->cgroups * ndt_ * 3 * 128 * 8;
-    size_t fr = 0, tot = 0;
-    if (ndt_ >= 4 && !form_choice(pl).two_pass && hipMemGetInfo(&fr, &tot) == hipSuccess &&
-        (pl->csum.bytes >= need_cs || need_cs + need_pb < fr / 2) && alloc_write_stream(pl->csum, need_cs) == TEMX_OK &&
-        pl->pbuf.ensure(need_pb) == TEMX_OK) {
-      HIPCHK(hipMemset(pl->csum.p, 0, pl->csum.bytes));
-      HIPCHK(hipMemset(pl->pbuf.p, 0, pl->pbuf.bytes));
-      const int64_t cunits = std::max<int64_t>(1, pl->cbatches / 4);
-      pl->sp_cproj4 = choose_split(D, cunits, TEMX_CLS_OP_WPS * pl->num_cu, 4, 8);
-      pl->sp_cflux = choose_split(D, std::max<int64_t>(1, pl->cgroups / (8 / edpw)), pl->num_cu, edpw, TEMX_CLS_MINCHUNK);
-      pl->sp_lflux = choose_split(D, std::max<int64_t>(1, pl->cgroups / 8), pl->num_cu, 1, TEMX_CLS_MINCHUNK);
-      const size_t need4 = (size_t)pl->sp_cflux.nsplit * 4 * 64 * D * 8;
-      if ((rc = pl->partial.ensure(std::max(need4, pl->partial.bytes)))) return rc;
-      if ((rc = pl->Bs.ensure((size_t)4 * 64 * D * 8))) return rc;
-      const int2* cuts_unused = nullptr;
-      if ((rc = class_cuts_dev(pl, pl->sp_cproj4.nsplit, &cuts_unused, true))) return rc;
-      pl->lone = true;
-    }
-  }
-  if (pl->cls) {
-    const bool quad = pick_dpw(ndt_, 4) == 4;
-    const int64_t cunits = std::max<int64_t>(1, pl->cbatches / 4);   // work units of ~4 batches (one cubed-sphere class-group)
-    pl->sp_cproj4 = choose_split(D, cunits, (quad ? 2 : CLS_PROJ_E_WPS) * pl->num_cu, quad ? 4 : 1, TEMX_CLS_MINCHUNK);
-    // one-pass form of sweep 1: quads of d-tiles, pieces of >= 8 class-groups (its cuts are group aligned)
-    Split sp_op = choose_split(D, cunits, TEMX_CLS_OP_WPS * pl->num_cu, 4, 8);
-    pl->sp_cproj1 = choose_split(D, cunits, CLS_PROJ_E_WPS * pl->num_cu, 4, TEMX_CLS_MINCHUNK);
-    pl->sp_ceddy = choose_split(D, cunits / (8 / edpw), pl->num_cu, edpw, TEMX_CLS_MINCHUNK);
-    const size_t need3 = (size_t)std::max({pl->sp_cproj4.nsplit * 4, pl->sp_ceddy.nsplit * (8 / edpw) * 3,
-                                           pl->sp_cproj1.nsplit}) * pl->K * D * 8;
-    if ((rc = pl->partial.ensure(std::max(need3, pl->partial.bytes)))) return rc;
-    // one-pass form: quads of d-tiles, enough class-groups per piece for group-aligned cuts to balance,
-    // and room for the class sums (8 x 512 B per class-group and d-tile)
-    pl->onepass = false;
-    pl->op_valid = false;
-    {
-      const FormChoice fc = form_choice(pl);
-      const bool force = fc.force_op;             // whenever possible (tests)
-      // a ragged last quad only idles a few waves.  The one-pass sweep runs one wave per SIMD, which
-      // pays once there is enough work: measured break-even near 1.2e7 elements per field
-      // (ne30x72x2, 7e6: 0.137 ms two-pass vs 0.156; ne30x72x4, 1.4e7: 0.223 vs 0.203;
-      // ne120x72x2, 1.1e8: 1.44 vs 1.18)
-      const bool quad_op = ndt_ >= 4 && (force || (double)pl->N * (double)D >= 1.2e7);
-      if (quad_op && !fc.two_pass) {
-        const size_t need_cs = (size_t)pl->cgroups * ndt_ * 8 * 64 * 8;   // 4 {north, south} pairs per lane
-        size_t fr = 0, tot = 0;
-        bool have = pl->csum.bytes >= need_cs;
-        if (!have && hipMemGetInfo(&fr, &tot) == hipSuccess && need_cs < fr / 2 && alloc_write_stream(pl->csum, need_cs) == TEMX_OK) {
-          // lanes beyond a ragged last d-tile are never written but are read (and ignored) by the flux kernel
-          HIPCHK(hipMemset(pl->csum.p, 0, pl->csum.bytes));
-          have = true;
-        }
-        if (have) {
-          pl->onepass = true;
-          pl->sp_cproj4 = sp_op;
-          pl->sp_cflux = choose_split(D, std::max<int64_t>(1, pl->cgroups / (8 / edpw)), pl->num_cu, edpw, TEMX_CLS_MINCHUNK);
-          const size_t need4 = (size_t)std::max(pl->sp_cflux.nsplit * 3, sp_op.nsplit * 7) * pl->K * D * 8;
-          if ((rc = pl->partial.ensure(std::max(need4, pl->partial.bytes)))) return rc;
-          if ((rc = pl->Pq.ensure((size_t)3 * pl->K * D * 8))) return rc;
-          // TEM + one tracer in one sweep: the four waves of a workgroup share a d-tile (one workgroup per CU)
-          pl->sp_copw = choose_split(D, std::max<int64_t>(1, cunits / 4), pl->num_cu, 1, 8);
-          // single-sweep form of temx_tem_run (no class-sum stream), the default where the one-pass path runs
-          // and the grid has enough latitude classes for the reference fit; TEMX_SINGLE_SWEEP=0 keeps the
-          // class-sum form, =1 also takes it on small grids
-          {
-            const bool off = fc.os == 0, forced = fc.os == 1;
-            // Both forms cost in proportion to D; the class-sum form also in proportion to the rows (its store stream and
-            // the flux kernel), the single sweep pays a pre-pass and a contraction that do not depend on them.  Measured
-            // break-even near 600 class-groups (ne30, 760 groups: 2.49 against 2.80 ms at 72 x 91, 0.86 against 0.96 at
-            // 72 x 30; round 3, with the contraction in LDS and 96 groups in the pre-pass: 2048).
-            const int64_t min_groups = pl->opt_single_sweep_min_groups >= 0 ? pl->opt_single_sweep_min_groups : 640;
-            bool want = !off && os_supported(pl) && (forced || pl->cgroups >= min_groups);
-            if (want) {
-              rc = build_os_tables(pl);
-              if (rc == TEMX_ERANK) want = false;          // too few distinct latitudes in the subsample: class-sum form
-              else if (rc) return rc;
-            }
-            if (want) {
-              pl->sp_os = choose_split(D, cunits, pl->num_cu, 4, 8);
-              // (one round of workgroups: the pre-pass is all prologue and epilogue)
-              // (the pre-pass stores next to nothing since round 4, so it may be cut as finely as the chip has CUs: at
-              //  D = 6552 one split per column quad left it on 103 workgroups, 0.18 ms for 430 MB)
-              pl->sp_os_s = choose_split(D, std::max<int64_t>(1, pl->sbatches / 4), pl->num_cu, 4, 2);
-              const size_t per = ((size_t)4 * pl->KX + 3 * pl->K) * D * 8;
-              if ((rc = pl->partial.ensure(std::max((size_t)std::max(pl->sp_os.nsplit, pl->sp_os_s.nsplit) * per, pl->partial.bytes)))) return rc;
-              if ((rc = pl->Ax.ensure(((size_t)4 * pl->KX + 3 * pl->K) * D * 8))) return rc;
-              if ((rc = pl->Axs.ensure((size_t)4 * pl->KR * D * 8))) return rc;
-              if ((rc = pl->osAt.ensure((size_t)4 * pl->NQ * D * 8))) return rc;
-              if ((rc = pl->osAb.ensure((size_t)4 * pl->NQ * D * 8))) return rc;
-              if ((rc = pl->rho.ensure((size_t)4 * pl->KR * D * 8))) return rc;
-              if ((rc = pl->rho0.ensure((size_t)4 * pl->KR * D * 8))) return rc;
-              HIPCHK(hipMemset(pl->rho0.p, 0, pl->rho0.bytes));
-              const int2* cu = nullptr;
-              if ((rc = os_cuts_dev(pl, false, pl->sp_os.nsplit, &cu))) return rc;
-              if ((rc = os_cuts_dev(pl, true, pl->sp_os_s.nsplit, &cu))) return rc;
-              pl->os_on = true;
-            }
-          }
-        }
-      }
-    }
-    // work cuts now, not at the first launch: launches must stay legal inside a stream capture
-    const int2* cuts_unused = nullptr;
-    if (pl->onepass && (rc = class_cuts_dev(pl, pl->sp_cproj4.nsplit, &cuts_unused, true))) return rc;
-    if (pl->onepass && (rc = class_cuts_dev(pl, pl->sp_copw.nsplit * 4, &cuts_unused, true))) return rc;
-    for (int nsub : {pl->sp_cproj4.nsplit, pl->sp_cproj1.nsplit, pl->sp_ceddy.nsplit * (8 / edpw)})
-      if ((rc = class_cuts_dev(pl, nsub, &cuts_unused))) return rc;
-  }
-  if (pl->sym) {
-    const int64_t nch = (pl->npg + SYM_PROJ_CH - 1) / SYM_PROJ_CH;
-    pl->sp_sproj4 = Split();
-    pl->sp_sproj1 = Split();
-    if (pick_dpw(ndt_, 4) == 4) {     // quads of d-tiles, all four fields per wave
-      pl->sp_sproj4 = choose_split(D, nch, 2 * pl->num_cu, 4);
-      pl->sp_sproj1 = choose_split(D, nch, 2 * pl->num_cu, 4);
-    } else {                          // small ragged D: one d-tile per workgroup, one field per wave
-      pl->sp_sproj4 = choose_split(D, nch, SYM_PROJ_E_WPS * pl->num_cu, 1);
-    }
-    pl->sp_seddy = choose_split(D, pl->npg / (8 / edpw), pl->num_cu, edpw);
-    const size_t need2 = (size_t)std::max({pl->sp_sproj4.nsplit * 4, pl->sp_seddy.nsplit * (8 / edpw) * 3,
-                                           pl->sp_sproj1.nsplit}) * pl->K * D * 8;
-    if ((rc = pl->partial.ensure(std::max(need2, pl->partial.bytes)))) return rc;
-  }
+  // what runs, how it is cut and what it needs: tem_layout.hpp.  `partial` grows stage by stage, as far as the stages
+  // that apply ask for; the class-sum stream csum is placed after the first of them.
+  const TemDims d = tem_dims(pl);
+  const FormChoice fc = form_choice(pl);
+  const BaseLayout b = tem_base_layout(d);
+  pl->sp_proj4 = b.sp_proj4;
+  pl->sp_eddy = b.sp_eddy;
+  pl->sp_proj1 = b.sp_proj1;
+  if ((rc = pl->partial.ensure(b.partial))) return rc;
+  if ((rc = pl->B4.ensure(b.B4))) return rc;
+  if ((rc = pl->B3.ensure(b.B3))) return rc;
+  if ((rc = pl->C4.ensure(b.C4))) return rc;
+  if ((rc = pl->zb.ensure(b.zb))) return rc;
+  if ((rc = pl->partial.ensure(b.partial_unfused))) return rc;
+  if (pl->lcls && (rc = set_tem_large_cls(pl, d, fc))) return rc;
+  if (pl->cls && (rc = set_tem_cls(pl, d, fc))) return rc;
+  if (pl->sym && (rc = set_tem_sym(pl, d))) return rc;
   if (bin_mode(pl) && (rc = bin_set_tem(pl))) return rc;   // tables (first time) and the workspace of the binned sweeps
   pl->tem = true;
   return TEMX_OK;
@@ -3334,7 +3258,7 @@ static int bin_workspace(temx_plan* pl, int64_t D, int NF) {
   if ((rc = pl->bin_cm.ensure(need_cm))) return rc;
   if ((rc = pl->bin_z.ensure(need_z))) return rc;
   if ((rc = pl->bin_cy.ensure(need_cy))) return rc;
-  return pl->partial.ensure(std::max(need_p, pl->partial.bytes));
+  return pl->partial.ensure(need_p);
 }
 
 static int bin_set_tem(temx_plan* pl) {
@@ -3536,14 +3460,13 @@ int temx_tem_eddy_rows(temx_plan* pl, const void* ua, const void* va, const void
 
 // ---- tracer TEM -----------------------------------------------------------------------------------
 static int tracer_ws(temx_plan* pl) {
-  const int64_t D = pl->D;
+  const TracerWs w = tracer_ws_layout(tem_dims(pl), pl->sp_proj1, pl->sp_cproj1);
   int rc;
-  if ((rc = pl->Bq.ensure((size_t)pl->K * D * 8))) return rc;
-  if ((rc = pl->Bq2.ensure((size_t)2 * pl->K * D * 8))) return rc;
-  if ((rc = pl->Ct.ensure((size_t)3 * pl->K4 * D * 8))) return rc;
-  if ((rc = pl->tz.ensure((size_t)3 * pl->M * D * 8))) return rc;
-  const size_t need = (size_t)std::max(pl->sp_proj1.nsplit, pl->sp_cproj1.nsplit) * pl->K * D * 8;
-  return pl->partial.ensure(std::max(need, pl->partial.bytes));
+  if ((rc = pl->Bq.ensure(w.Bq))) return rc;
+  if ((rc = pl->Bq2.ensure(w.Bq2))) return rc;
+  if ((rc = pl->Ct.ensure(w.Ct))) return rc;
+  if ((rc = pl->tz.ensure(w.tz))) return rc;
+  return pl->partial.ensure(w.partial);
 }
 
 int temx_tracer_stage1(temx_plan* pl, const void* q, int dtype, double* Bq, void* stream) try {
@@ -3702,7 +3625,7 @@ int temx_tem_tracer_stage1(temx_plan* pl, const void* ua, const void* va, const 
   const int64_t KD = (int64_t)pl->K * pl->D;
   if ((rc = pl->csq.ensure((size_t)pl->cgroups * sp.ndt * 2 * 64 * 8))) return rc;
   if ((rc = pl->Pq2.ensure((size_t)2 * KD * 8))) return rc;
-  if ((rc = pl->partial.ensure(std::max((size_t)sp.nsplit * 10 * KD * 8, pl->partial.bytes)))) return rc;
+  if ((rc = pl->partial.ensure(tem_tracer_stage1_partial(tem_dims(pl), sp)))) return rc;
   set_tail(pl, 0, pl->nt);
   pl->op_valid = pl->c4_valid = pl->tq_valid = pl->os_valid = false;
   FieldPtrs<5> fp;
