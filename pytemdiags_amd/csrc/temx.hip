@@ -12,6 +12,7 @@
 #include "../../include/temx_gclim.h"
 #include "../include/temx_mgclim.h"
 #include "../include/temx_wave.h"
+#include "../include/temx_tfilt.h"
 
 #include <hip/hip_runtime.h>
 
@@ -47,6 +48,7 @@
 #include "kernels_gclim.hpp"
 #include "kernels_mgclim.hpp"
 #include "kernels_wave.hpp"
+#include "kernels_tfilt.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
 #include "bin_tables.hpp"
 #include "class_tables.hpp"
@@ -59,6 +61,7 @@
 #include "launch_shapes.hpp"
 #include "mgclim_shapes.hpp"
 #include "tem_layout.hpp"
+#include "tfilt_shapes.hpp"
 #include "wave_tables.hpp"
 
 using namespace temx;
@@ -1554,6 +1557,26 @@ static int launch_time_sum(const ClimPtrs& fp, int nf, int64_t rows, int64_t nt,
   } else {
     hipLaunchKernelGGL((time_sum_long_kernel<T>), dim3((unsigned)sh.nblk, (unsigned)nf), dim3(CLIM_THREADS), 0, st, fp, rows, nt,
                        accumulate);
+  }
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+// ---- the time filter (../include/temx_tfilt.h, kernels_tfilt.hpp): the nf sources of one element type T ----
+template <typename T, typename D>
+static int launch_tfilt(const TfiltPtrs& fp, int nf, int nb, const double* w, int64_t rows, int64_t nt, int nw, hipStream_t st) {
+  const TfiltShape sh = tfilt_shape(rows, nt, nw, nb, sizeof(T), sizeof(D));
+  if (sh.grid >= TFILT_GRID_MAX)
+    return fail(TEMX_EUNSUPPORTED, "too many rows for one launch (%lld workgroups): filter the fields in parts along ncol",
+                (long long)sh.grid);
+  if (tfilt_lds_bytes(sh, sizeof(T)) > (size_t)TFILT_LDS_BYTES || sh.TT < TFILT_R || sh.TT % TFILT_R)
+    return fail(TEMX_EINTERNAL, "staged rows of the time filter exceed their LDS budget");
+  const dim3 grid((unsigned)sh.grid, (unsigned)nf), block(TFILT_THREADS);
+  switch (nb) {
+    case 1: hipLaunchKernelGGL((tfilt_kernel<T, D, 1>), grid, block, 0, st, fp, w, rows, nt, nw, sh); break;
+    case 2: hipLaunchKernelGGL((tfilt_kernel<T, D, 2>), grid, block, 0, st, fp, w, rows, nt, nw, sh); break;
+    case 3: hipLaunchKernelGGL((tfilt_kernel<T, D, 3>), grid, block, 0, st, fp, w, rows, nt, nw, sh); break;
+    default: hipLaunchKernelGGL((tfilt_kernel<T, D, 4>), grid, block, 0, st, fp, w, rows, nt, nw, sh); break;
   }
   HIPCHK(hipGetLastError());
   return TEMX_OK;
@@ -4356,6 +4379,50 @@ int temxk_wave_timing_read(temxk_wave* w, double* sum_ms, int* launches) try {
   }
   *sum_ms = tot;
   *launches = (int)w->timed.size();
+  return TEMX_OK;
+} TEMX_CATCH
+
+// ---- EP flux by time scale: the filter along the time axis (../include/temx_tfilt.h, kernels_tfilt.hpp) ----
+int temxf_version(void) { return 100; }
+
+int temxf_filter_time(int device, int nf, const void* const* src_host, const int* src_dtype_host, int nb, void* const* dst_host,
+                      int dst_dtype, int64_t ncol, int nlev, int64_t nt, int nw, const double* weights, int flags,
+                      void* stream) try {
+  ARGCHK(tfilt_check_args(nf, src_host, src_dtype_host, nb, dst_host, dst_dtype, ncol, nlev, nt, nw, weights, flags));
+  const int64_t rows = ncol * nlev;
+  // the fp64 and the fp32 sources go in a launch each: their rows are cut differently (tfilt_shapes.hpp)
+  TfiltPtrs p64{}, p32{};
+  int n64 = 0, n32 = 0;
+  for (int f = 0; f < nf; ++f) {
+    TfiltPtrs& p = src_dtype_host[f] == TEMX_F64 ? p64 : p32;
+    int& n = src_dtype_host[f] == TEMX_F64 ? n64 : n32;
+    p.src[n] = src_host[f];
+    for (int b = 0; b < nb; ++b) p.dst[b][n] = dst_host[b * nf + f];
+    ++n;
+  }
+  for (const size_t esz : {sizeof(double), sizeof(float)})   // every refusal before the first launch
+    if ((esz == 8 ? n64 : n32) && tfilt_shape(rows, nt, nw, nb, esz, dtype_size(dst_dtype)).grid >= TFILT_GRID_MAX)
+      return fail(TEMX_EUNSUPPORTED, "too many rows for one launch: filter the fields in parts along ncol");
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = S_(stream);
+  int rc;
+  if (n64 && (rc = launch_tfilt<double, double>(p64, n64, nb, weights, rows, nt, nw, st))) return rc;
+  if (n32 && dst_dtype == TEMX_F64 && (rc = launch_tfilt<float, double>(p32, n32, nb, weights, rows, nt, nw, st))) return rc;
+  if (n32 && dst_dtype == TEMX_F32 && (rc = launch_tfilt<float, float>(p32, n32, nb, weights, rows, nt, nw, st))) return rc;
+  return TEMX_OK;
+} TEMX_CATCH
+
+// tfilt_shape of tfilt_shapes.hpp, for callers that want the edges of the cut (no device, no state)
+int temxf_filter_shape(int64_t rows, int64_t nt, int nw, int nb, int src_esz, int dst_esz, int* shape_host) try {
+  ARGCHK(check_null(shape_host, "shape_host") | tfilt_check_sizes(rows, 1, nt, nw, nb));
+  if ((src_esz != 4 && src_esz != 8) || (dst_esz != 4 && dst_esz != 8)) return fail(TEMX_EINVAL, "src_esz and dst_esz must be 4 or 8");
+  if (src_esz == 8 && dst_esz == 4) return fail(TEMX_EINVAL, "src_esz is 8 but dst_esz is 4: an fp64 source has no fp32 destination");
+  const TfiltShape s = tfilt_shape(rows, nt, nw, nb, (size_t)src_esz, (size_t)dst_esz);
+  if (s.grid >= TFILT_GRID_MAX)
+    return fail(TEMX_EUNSUPPORTED, "too many rows for one launch (%lld workgroups): filter the fields in parts along ncol",
+                (long long)s.grid);
+  const int v[7] = {s.rpb, s.TT, s.stride, s.R, s.ntile, (int)s.grid, (int)tfilt_lds_bytes(s, (size_t)src_esz)};
+  std::copy(v, v + 7, shape_host);
   return TEMX_OK;
 } TEMX_CATCH
 

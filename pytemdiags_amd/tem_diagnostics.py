@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib, containers, layout
 from . import climatology as clim
+from . import timebands as tb
 from . import waves as wv
 from .constants import P0, Om
 from .sph_zonal_mean import sph_zonal_averager
@@ -44,12 +45,18 @@ class TEMDiagnostics:
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
                  lat_bins=None, climatology=False, tracer_mask=None, min_time_coverage=None, time_groups=None,
-                 time_weights=None, min_group_coverage=None, lon=None, wavenumbers=None):
+                 time_weights=None, min_group_coverage=None, lon=None, wavenumbers=None, time_bands=None):
         # ---- zonal wavenumbers (not in the reference; waves.py): checked before anything touches the device ----
         self._waves, self._wave_args = None, None
         if wavenumbers is not None:
             self._wave_args = wv.check_arguments(wavenumbers, lon, len(lat_native), L, missing=missing, lat_bins=lat_bins,
                                                  time_block=time_block, climatology=climatology)
+        # ---- EP flux by time scale (not in the reference; timebands.py): checked before anything touches the device ----
+        # (the record's length is checked in _config_dims, still before the device)
+        self._bands, self._band_args = None, None
+        if time_bands is not None:
+            self._band_args = tb.check_arguments(time_bands, missing=missing, time_block=time_block, climatology=climatology,
+                                                 wavenumbers=wavenumbers)
         # ---- time-mean TEM (not in the reference; climatology.py): checked before anything touches the device ----
         self.min_group_coverage = clim.check_group_coverage(min_group_coverage, climatology, missing, time_groups,
                                                             time_weights, min_time_coverage)
@@ -123,10 +130,13 @@ class TEMDiagnostics:
             else:
                 self._clim = (clim.Builder(self, plan) if self.min_time_coverage is None
                               else clim.MaskedBuilder(self, plan, self.min_time_coverage))
+        self._band_builder = None if self._band_args is None else tb.Builder(self, plan, self._band_args)
         if self.time_block is None and self._block_source is None:
             if self._clim is not None:      # time means and their TEM first: the ordinary run is the plan's last
                 self._clim.add(self._dev_fields)
                 self._clim.run_stationary()
+            if self._band_builder is not None:      # the band runs first too, for the same reason
+                self._band_builder.run(self._dev_fields)
             plan.set_tem(self.NLEV, self.NT, self._p_np, float(self.p0))
             self._res, self._zon, self._cov, self._tres, self._tzon, self._tcov = self._run_block(
                 plan, self._dev_fields, self._dev_q, self.NT)
@@ -135,6 +145,9 @@ class TEMDiagnostics:
         if self._clim is not None:
             self._climatology = self._clim.finish(self._zon)
             self._clim = None
+        if self._band_builder is not None:  # the plan is still set for the ordinary run, whose mean state the sets share
+            self._bands = self._band_builder.finish(self._zon)
+            self._band_builder = None
         if self._wave_args is not None:     # the plan is still set for the ordinary run, whose zonal means the sets share
             self._waves = wv.build(self, plan, self._wave_args[1], self._wave_args[0], self._dev_fields, self._zon)
 
@@ -145,6 +158,15 @@ class TEMDiagnostics:
         if self._waves is None:
             raise RuntimeError("waves is not available: build the object with lon= and wavenumbers=")
         return self._waves
+
+    @property
+    def bands(self):
+        """``time_bands={name: weights, ...}``: the result sets by time scale, ``timebands.TEMBands`` (``tem.bands[name]``,
+        ``tem.bands.residual``, ``tem.bands.time_mean()``, ``names``, ``half_width``, ``weights``, ``filter_path``,
+        ``workspace_bytes``)."""
+        if self._bands is None:
+            raise RuntimeError("bands is not available: build the object with time_bands=")
+        return self._bands
 
     @property
     def climatology(self):
@@ -246,6 +268,9 @@ class TEMDiagnostics:
                         # one block whose fields are kept: as in a whole run, the ordinary run is the plan's last
                         self._clim.run_stationary()
                         cur = None
+                if self._band_builder is not None:      # (one block whose fields are kept: time_block= is refused)
+                    self._band_builder.run(fs[:4])
+                    cur = None
                 if ntb != cur:
                     plan.set_tem(self.NLEV, ntb, self._p_np, float(self.p0))
                     cur = ntb
@@ -343,6 +368,10 @@ class TEMDiagnostics:
             wv.check_arguments(kw["wavenumbers"], kw.get("lon"), len(lat_native), kw.get("L", 50), missing=kw.get("missing", "raise"),
                                lat_bins=kw.get("lat_bins"), time_block=kw.get("time_block"),
                                climatology=kw.get("climatology", False))
+        if kw.get("time_bands") is not None:
+            tb.check_record(tb.check_arguments(kw["time_bands"], missing=kw.get("missing", "raise"), time_block=kw.get("time_block"),
+                                               climatology=kw.get("climatology", False), wavenumbers=kw.get("wavenumbers")),
+                            cls._record_times(ua, kw.get("dims"), kw.get("dim_names", DEFAULT_DIMS), kw.get("time"))[0])
         mgc = clim.check_group_coverage(kw.get("min_group_coverage"), kw.get("climatology", False), kw.get("missing", "raise"),
                                         kw.get("time_groups"), kw.get("time_weights"), kw.get("min_time_coverage"))
         clim.check_flag(kw.get("climatology", False), kw.get("missing", "raise"), kw.get("min_time_coverage"), mgc)
@@ -652,6 +681,10 @@ class TEMDiagnostics:
         # ---- grouped and weighted time means (climatology.py): labels and weights against the record, on the host ----
         if self._group_args is not None:
             self._groups = clim.resolve_groups(*self._group_args, self.NT, self.time)
+
+        # ---- EP flux by time scale (timebands.py): the record against the filter's length, on the host ----
+        if self._band_args is not None:
+            tb.check_record(self._band_args, self.NT)
 
         # ---- device residency: contiguous [ncol][plev][time], one dtype ----
         dts = {v.dtype for v in vals.values()}
