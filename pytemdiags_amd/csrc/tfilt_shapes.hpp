@@ -40,7 +40,7 @@ struct TfiltShape {
 
 inline size_t tfilt_lds_bytes(const TfiltShape& s, size_t src_esz) { return (size_t)s.rpb * s.stride * src_esz; }
 
-// rows, nt >= nw, nw odd in 3..TFILT_NW_MAX, src_esz 4 or 8 (tfilt_check_sizes has seen them).  nb and dst_esz do not move
+// rows, nt >= nw, nw odd in 1..TFILT_NW_MAX, src_esz 4 or 8 (tfilt_check_sizes has seen them).  nb and dst_esz do not move
 // the cut: the bands of an output share its window and the outputs go from registers to memory.
 inline TfiltShape tfilt_shape(int64_t rows, int64_t nt, int nw, int /*nb*/, size_t src_esz, size_t /*dst_esz*/) {
   TfiltShape s{};

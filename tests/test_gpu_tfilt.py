@@ -6,8 +6,18 @@ fp32 at the end for an fp32 destination.  It is evaluated once per row of a smal
 are made of those rows (a record of ``nt`` times holds their first ``nt`` elements), so an output is looked up, not
 computed again -- which is the contract: the bits of an output depend on its window, the weights and the dtypes, not on
 where the row lies, how long the record is or how the launch is cut.  The edges of the cut come from
-``temxf_filter_shape``."""
+``temxf_filter_shape``.
+
+Two pools.  ``"f64"`` / ``"f32"``: random normal numbers between 1e-3 and 1e3.  ``"x64"`` / ``"x32"`` (``edge_pool``):
+hand-placed values of the source type -- subnormals, signed zeros, the largest finite value and its negative, values
+around the smallest normal number whose products with weights below 1 are subnormal, equal and opposite neighbours that
+cancel exactly -- for tests/test_gpu_tfilt_edges.py.  ``exact_fma`` carries them: ``float(Fraction)`` is correctly rounded
+into the subnormal range and keeps the sign of an underflow, an exact zero gets the sign IEEE 754 gives it under round to
+nearest, and the one rounding to fp32 is ``np.float32(acc)``, which overflows to inf.  The fp64 accumulator itself must
+stay finite (``float(Fraction)`` raises OverflowError otherwise): that is the caller's choice of weights, and the largest
+finite values of the edge pool stand at least 20 elements apart for it."""
 import ctypes as C
+import math
 from fractions import Fraction
 
 import numpy as np
@@ -23,8 +33,41 @@ SENTINEL = {8: -6.02214076e23, 4: np.float32(-6.02214076e23)}
 _pool, _oracle = {}, {}
 
 
+def edge_pool(kind):
+    """``[POOL][LMAX]`` hand-placed rows, float64 (``"x64"``) or float32 (``"x32"``), in stretches of 50 elements: (0) only
+    values of at most four times the smallest normal number -- subnormals, both zeros, neighbours of the smallest normal
+    -- so that whole windows of them give subnormal and underflowing sums; (1) moderate numbers with equal and opposite
+    neighbours, both zeros among them; (2) a mixture of the two with the largest finite value, sign alternating, at every
+    25th element, so that no window of fewer than 25 weights holds two of them; (3) runs of ten equal values of list
+    (0), which weights that sum to 0 take to a sum far below the smallest subnormal, or to an exact zero.  Row p walks
+    the lists with a step of its own (1, 5, 7: coprime to their lengths), so different neighbours meet in different
+    rows."""
+    t = np.float64 if kind == "x64" else np.float32
+    fi = np.finfo(t)
+    tiny, den, big, eps = float(fi.tiny), float(fi.smallest_subnormal), float(fi.max), float(fi.eps)
+    small = [den, -den, 3 * den, tiny, -tiny, tiny - den, 1.5 * tiny, -1.5 * tiny, 0.0, -0.0, 2 * tiny, -(tiny + den), 5 * den,
+             -0.0, 0.0, -3 * tiny]
+    moderate = [1.5, 1.5, -1.5, -1.5, 0.0, -0.0, 3.25, -3.25, 1 + eps, -(1 + eps), 0.1, 0.1]
+    a = np.zeros((POOL, LMAX), dtype=t)
+    for p, step in enumerate((1, 5, 7)):
+        for i in range(LMAX):
+            seg = (i // 50) % 4
+            v = small[i * step % 16] if seg == 0 or (seg == 2 and i % 2) else moderate[i * step % 12]
+            if seg == 3:
+                v = small[i // 10 * step % 16]
+            if seg == 2 and i % 25 == 7 + p:
+                v = big if (i // 25) % 2 else -big
+            a[p, i] = v
+    return a
+
+
 def pool(kind):
-    """``[POOL][LMAX]`` rows of mixed magnitude, float64 or float32 (built once, never written to)."""
+    """``[POOL][LMAX]`` rows of mixed magnitude, float64 or float32 (built once, never written to); ``"x64"`` / ``"x32"``:
+    the hand-placed rows of ``edge_pool``."""
+    if kind not in _pool and kind in ("x64", "x32"):
+        a = edge_pool(kind)
+        a.setflags(write=False)
+        _pool[kind] = a
     if kind not in _pool:
         rng = np.random.default_rng(11 if kind == "f64" else 12)
         a = rng.standard_normal((POOL, LMAX)) * 10.0 ** rng.integers(-3, 4, size=(POOL, LMAX))
@@ -40,19 +83,36 @@ def weights(nw, nb):
     return np.ascontiguousarray(rng.standard_normal((nb, nw)) / np.sqrt(nw))
 
 
+def exact_fma(fw, fx, acc, w, x):
+    """``fma(w, x, acc)`` of finite doubles, correctly rounded (``fw``, ``fx``: ``w`` and ``x`` as Fractions).  A sum that
+    is not zero goes through ``float(Fraction)``: correctly rounded, subnormals included, and a result that underflows
+    keeps its sign.  An exact zero is ``-0.0`` only where the product and the addend are both negative zeros, and ``+0.0``
+    otherwise (round to nearest: ``x + (-x) = +0``, ``(+0) + (-0) = +0``)."""
+    s = fw * fx + Fraction(acc)
+    if s:
+        return float(s)
+    if acc == 0.0 and math.copysign(1.0, acc) < 0 and (w == 0.0 or x == 0.0) and math.copysign(1.0, w) * math.copysign(1.0, x) < 0:
+        return -0.0
+    return 0.0
+
+
 def oracle(kind, p, w, nto, out32):
-    """The first ``nto`` outputs of pool row ``p`` under the weights ``w`` ``[nw]``: exact fma chain in Fractions."""
+    """The first ``nto`` outputs of pool row ``p`` under the weights ``w`` ``[nw]``: exact fma chain in Fractions, one
+    rounding to fp32 at the end for an fp32 destination (overflow to inf included)."""
     key = (kind, p, w.tobytes(), out32)
     have = _oracle.get(key, np.zeros(0))
     if have.size < nto:
-        row = [Fraction(float(v)) for v in pool(kind)[p]]
-        fw = [Fraction(float(v)) for v in w]
+        xs = [float(v) for v in pool(kind)[p]]
+        ws = [float(v) for v in w]
+        row = [Fraction(v) for v in xs]
+        fw = [Fraction(v) for v in ws]
         out = list(have)
         for t in range(have.size, nto):
             acc = 0.0
             for k, wk in enumerate(fw):
-                acc = float(wk * row[t + k] + Fraction(acc))
-            out.append(np.float32(acc) if out32 else acc)
+                acc = exact_fma(wk, row[t + k], acc, ws[k], xs[t + k])
+            with np.errstate(over="ignore"):
+                out.append(np.float32(acc) if out32 else acc)
         have = np.array(out, dtype=np.float32 if out32 else np.float64)
         _oracle[key] = have
     return have[:nto]

@@ -181,6 +181,75 @@ def test_tfilt_shape_through_the_library():
     assert rc == EUNSUPPORTED and "in parts along ncol" in msg, (rc, msg)
 
 
+# ---- the oracle of the GPU tests, on its own --------------------------------------------------------------------------
+def test_fraction_oracle_rounds_subnormals_signs_zeros_and_overflows_fp32():
+    """``exact_fma`` and ``oracle`` of tests/test_gpu_tfilt.py against constants derived by hand (this Python has no
+    ``math.fma``): ties to even in the subnormal range, the sign of an underflow, the signs of exact zeros under round to
+    nearest, one rounding instead of two, and the final rounding to fp32 with its subnormals and its overflow to inf.
+    The random pools give the numbers the plain Fraction chain gives."""
+    from fractions import Fraction as Fr
+
+    import test_gpu_tfilt as tf
+    den = 2.0 ** -1074
+
+    def fma(w, x, acc):
+        return tf.exact_fma(Fr(w), Fr(x), acc, w, x)
+
+    def same(a, b):
+        return a == b and math.copysign(1.0, a) == math.copysign(1.0, b)
+
+    assert same(fma(0.5, den, 0.0), 0.0)                      # 2^-1075: a tie, to even
+    assert same(fma(0.5, 3 * den, 0.0), 2 * den)              # 1.5 den: a tie, to even
+    assert same(fma(0.75, den, 0.0), den) and same(fma(0.25, den, 0.0), 0.0)
+    assert same(fma(-0.25, den, 0.0), -0.0) and same(fma(0.25, -den, 0.0), -0.0)          # an underflow keeps its sign
+    assert same(fma(-0.75, den, 0.0), -den) and same(fma(0.5, 2.0 ** -1022, 0.0), 2.0 ** -1023)
+    assert same(fma(1 + 2.0 ** -52, 1 + 2.0 ** -52, -(1 + 2.0 ** -51)), 2.0 ** -104)      # one rounding, not two
+    assert same(fma(2.0 ** -537, 2.0 ** -537, den), 2 * den)  # the product alone underflows; the sum is exact
+    assert same(fma(1.0, -0.0, 0.0), 0.0) and same(fma(1.0, -0.0, -0.0), -0.0) and same(fma(-1.0, 0.0, -0.0), -0.0)
+    assert same(fma(-1.0, -0.0, -0.0), 0.0) and same(fma(0.0, 5.0, -0.0), 0.0) and same(fma(-0.0, 5.0, -0.0), -0.0)
+    assert same(fma(1.5, 2.0, -3.0), 0.0) and same(fma(-1.5, 2.0, 3.0), 0.0)              # x + (-x) = +0
+    assert same(fma(0.0, 5.0, 7.0), 7.0) and same(fma(2.0, 0.0, -den), -den)
+    # the rounding to fp32 the oracle applies
+    d32 = 2.0 ** -149
+    with np.errstate(over="ignore"):
+        assert np.float32(0.75 * d32) == np.float32(d32) and np.float32(1.5 * d32) == np.float32(2 * d32)
+        z = np.float32(-0.25 * d32)
+        assert z == 0 and np.signbit(z) and np.isinf(np.float32(4.0 * float(np.finfo(np.float32).max)))
+    # the edge pools hold what their docstring says, exactly, and the oracle carries them
+    for kind, t in (("x64", np.float64), ("x32", np.float32)):
+        a = tf.pool(kind)
+        fi = np.finfo(t)
+        assert a.dtype == t and a.shape == (tf.POOL, tf.LMAX) and np.isfinite(a).all()
+        sub = (a != 0) & (np.abs(a) < fi.tiny)
+        assert sub.any() and np.signbit(a[a == 0]).any() and not np.signbit(a[a == 0]).all()
+        assert (a == fi.max).any() and (a == -fi.max).any() and (np.abs(a) == fi.smallest_subnormal).any()
+        for p in range(tf.POOL):
+            at = np.flatnonzero(np.abs(a[p]) == fi.max)
+            assert at.size >= 8 and np.diff(at).min() >= 20
+    w4 = np.array([4.0, -4.0, 4.0, -4.0, 4.0])
+    got = tf.oracle("x32", 0, w4, 300, True)
+    assert got.dtype == np.float32 and np.isposinf(got).any() and np.isneginf(got).any() and not np.isnan(got).any()
+    wide = tf.oracle("x32", 0, w4, 300, False)
+    assert np.isfinite(wide).all() and np.abs(wide).max() == 4.0 * float(np.finfo(np.float32).max)
+    half = np.array([0.25, -0.5, 0.25])
+    for kind, out32, t in (("x64", False, np.float64), ("x32", True, np.float32)):
+        got = tf.oracle(kind, 1, half, 400, out32)
+        tiny = np.finfo(t).tiny
+        assert ((got != 0) & (np.abs(got) < tiny)).any() and np.signbit(got[got == 0]).any()
+    # the random pools: the plain chain, as before
+    w = tf.weights(5, 1)[0]
+    for kind, out32 in (("f64", False), ("f32", True), ("f32", False)):
+        row = [Fr(float(v)) for v in tf.pool(kind)[2]]
+        want = []
+        for t in range(20):
+            acc = 0.0
+            for k in range(5):
+                acc = float(Fr(float(w[k])) * row[t + k] + Fr(acc))
+            want.append(np.float32(acc) if out32 else acc)
+        want = np.array(want, dtype=np.float32 if out32 else np.float64)
+        assert np.array_equal(tf.bits(tf.oracle(kind, 2, w, 20, out32)), tf.bits(want))
+
+
 # ---- front-end refusals before the device -------------------------------------------------------------------------------
 def _tiny(nt=12):
     la = -90 + (np.arange(6) + 0.5) * 30.0
