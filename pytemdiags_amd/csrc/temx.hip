@@ -13,6 +13,7 @@
 #include "../include/temx_mgclim.h"
 #include "../include/temx_wave.h"
 #include "../include/temx_tfilt.h"
+#include "../include_wavecls/temx_wavecls.h"
 
 #include <hip/hip_runtime.h>
 
@@ -48,6 +49,7 @@
 #include "kernels_gclim.hpp"
 #include "kernels_mgclim.hpp"
 #include "kernels_wave.hpp"
+#include "kernels_wavecls.hpp"
 #include "kernels_tfilt.hpp"
 // host code without HIP: the tables, matrices and launch shapes of a plan
 #include "bin_tables.hpp"
@@ -62,6 +64,7 @@
 #include "mgclim_shapes.hpp"
 #include "tem_layout.hpp"
 #include "tfilt_shapes.hpp"
+#include "wave_class_tables.hpp"
 #include "wave_tables.hpp"
 
 using namespace temx;
@@ -1822,8 +1825,32 @@ static int wave_ensure(temxk_wave* w, int nf, int64_t D) {
   return w->C.ensure((size_t)nf * w->kc_max * D * 8);
 }
 
-// one wavenumber: basis, zonal table, Gm and its inverse, deflation by the plan's native zonal-mean operator
-static int wave_build_m(temxk_wave* w, WaveM& wm) {
+// class form (../include_wavecls/temx_wavecls.h, kernels_wavecls.hpp): what a wavenumber keeps instead of the deflated blocks
+struct WaveClsM {
+  WaveClsShape sh;
+  DevBuf tab;       // [cgroups + 1] class-group tables: the class basis, then -E and -O (wave_class_tables.hpp)
+  DevBuf cw;        // [cbatches + CLS_PADB][4][CLS_MB] {cos m lon, sin m lon} of the entries of crow
+};
+
+// the class-group tables of one wavenumber from Z = P Ym and the plan's class latitudes
+static int wavecls_gather(temx_plan* pl, int m, double pmm_norm, const double* Z, const int* rep, WaveClsM& cm) {
+  const int TBS = cm.sh.TBS;
+  const size_t bytes = (size_t)(pl->cgroups + 1) * wavecls_group_doubles(TBS) * 8;
+  int rc;
+  if ((rc = cm.tab.ensure(bytes))) return rc;
+  HIPCHK(hipMemset(cm.tab.p, 0, bytes));
+  hipLaunchKernelGGL(wavecls_basis_kernel, dim3((unsigned)((pl->ncls + 255) / 256)), dim3(256), 0, nullptr,
+                     (const double*)pl->xc.d(), pl->ncls, pl->cls_npad, m, pl->L, pmm_norm, TBS, cm.tab.d());
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(wavecls_defl_kernel, dim3((unsigned)((pl->ncls * cm.sh.Kc + 255) / 256)), dim3(256), 0, nullptr, Z, rep,
+                     pl->ncls, cm.sh.ndeg, TBS, cm.tab.d());
+  HIPCHK(hipGetLastError());
+  return TEMX_OK;
+}
+
+// one wavenumber: basis, zonal table, Gm and its inverse, deflation by the plan's native zonal-mean operator.  With cm
+// (the class form) the deflated blocks are not made: the class tables are gathered from P Ym and the blocks are freed.
+static int wave_build_m(temxk_wave* w, WaveM& wm, WaveClsM* cm = nullptr, const int* rep = nullptr) {
   temx_plan* pl = w->pl;
   const WaveShape& sh = wm.sh;
   const int m = wm.m, L = pl->L, Kc = sh.Kc;
@@ -1864,6 +1891,12 @@ static int wave_build_m(temxk_wave* w, WaveM& wm) {
   HIPCHK(hipMemcpy(wm.ginv.p, Gi.data(), Gi.size() * 8, hipMemcpyHostToDevice));
   // Ymd = Ym - P Ym with the plan's own operator (operator workspace of the plan only)
   if ((rc = temx_zonal_mean(pl, Ym.p, TEMX_F64, Kc, Z.d(), 1, nullptr))) return rc;
+  if (cm != nullptr) {
+    if ((rc = wavecls_gather(pl, m, pmm_norm, Z.d(), rep, *cm))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    wm.yblk.release();
+    return TEMX_OK;
+  }
   hipLaunchKernelGGL(wave_deflate_kernel, dim3((unsigned)((N * Kc + 255) / 256)), dim3(256), 0, nullptr, (const double*)Ym.d(),
                      (const double*)Z.d(), N, Kc, sh.gstride, wm.yblk.d());
   HIPCHK(hipGetLastError());
@@ -1879,6 +1912,61 @@ static int wave_plan_refused(const temx_plan* pl) {
     return fail(TEMX_EUNSUPPORTED, "zonal wavenumbers are not available on a plan finalised with a Gram matrix from outside "
                 "(an ncol-sharded job): the fit runs over all columns of the grid");
   return TEMX_OK;
+}
+
+// ---- the class form of the fit (../include_wavecls/temx_wavecls.h) ----
+// What the two forms share -- latitudes, Pz, Gm^-1, the workspace, the flag, the solve and the flux and parts kernels -- is
+// a generic state whose deflated blocks are never kept.
+struct temxz_wave {
+  temxk_wave g;
+  std::vector<WaveClsM> cm;     // per wavenumber, aligned with g.ms
+  ~temxz_wave() {
+    for (WaveClsM& c : cm) {
+      c.tab.release();
+      c.cw.release();
+    }
+  }
+};
+
+static int wavecls_plan_refused(const temx_plan* pl) {
+  if (int rc = wave_plan_refused(pl)) return rc;
+  if ((!pl->cls && !pl->lcls) || pl->h_crow.empty())
+    return fail(TEMX_EUNSUPPORTED, "the class form of the wave fit needs a plan with latitude classes (columns that share "
+                "latitudes); this plan has none: use the generic form");
+  return TEMX_OK;
+}
+
+// one field per wave: the four fields of a d-tile (NF = 4) or four d-tiles of one field (NF = 1) per workgroup
+template <int NF>
+static Split wavecls_split(const temx_plan* pl, int64_t D) {
+  return choose_split(D, std::max<int64_t>(1, pl->cbatches / 4), WAVECLS_WPS * pl->num_cu, NF == 1 ? 4 : 1, TEMX_CLS_MINCHUNK);
+}
+// X batches a wave holds (PD - 1 in flight): a batch of fp32 carries half the bytes
+template <typename T> constexpr int wavecls_pd() { return sizeof(T) == 4 ? 3 : 2; }
+
+// B[NF][Kc][D] = (Ym - P Ym)^T {fields} by the class sweep and the deterministic slab sum
+template <int NF>
+static int wavecls_sweep(temxz_wave* z, size_t mi, const FieldPtrs<NF>& fp, int dtype, int64_t D, const double* colscale,
+                         int sfield, double* B, hipStream_t st) {
+  temxk_wave* w = &z->g;
+  temx_plan* pl = w->pl;
+  const WaveClsM& cm = z->cm[mi];
+  const Split sp = wavecls_split<NF>(pl, D);
+  const int64_t n = (int64_t)NF * cm.sh.Kc * D;
+  int rc = w->partial.ensure((size_t)sp.nsplit * (size_t)n * 8);
+  if (rc) return rc;
+  const int2* cuts = nullptr;
+  if ((rc = class_cuts_dev(pl, sp.nsplit, &cuts))) return rc;
+  rc = by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return dispatch(WaveClsTBSValues{}, cm.sh.TBS, [&](auto tbs) {
+      return launch<wavecls_project_kernel<T, NF, decltype(tbs)::value, WAVECLS_WPS, wavecls_pd<T>()>>(
+          dim3(sp.grid), dim3(256), 0, st, fp, D, cm.sh.ndeg, (const double*)cm.tab.d(), static_cast<const int4*>(pl->crow.p),
+          static_cast<const double2*>(cm.cw.p), cuts, colscale, sfield, w->partial.d(), sp.nsplit, sp.ndt);
+    });
+  });
+  if (rc) return rc;
+  return wave_reduce(w, w->partial.d(), sp.nsplit, n, n, B, st);
 }
 
 extern "C" {
@@ -4379,6 +4467,169 @@ int temxk_wave_timing_read(temxk_wave* w, double* sum_ms, int* launches) try {
   }
   *sum_ms = tot;
   *launches = (int)w->timed.size();
+  return TEMX_OK;
+} TEMX_CATCH
+
+// ---- zonal wavenumbers on latitude classes (../include_wavecls/temx_wavecls.h, kernels_wavecls.hpp, wave_class_tables.hpp) ----
+int temxz_version(void) { return 100; }
+
+int temxz_wave_create(temxz_wave** out, temx_plan* pl, const double* lon_deg_host, int nm, const int* m_host) try {
+  if (!out) return fail(TEMX_EINVAL, "null argument");
+  *out = nullptr;
+  if (!pl) return fail(TEMX_EINVAL, "null plan");
+  if (!pl->finalized) return fail(TEMX_ESTATE, "plan not finalised");
+  char msg[256];
+  if (const int code = wave_check_args(pl->L, pl->N, lon_deg_host, nm, m_host, msg, sizeof msg)) return fail(code, "%s", msg);
+  if (int rc = wavecls_plan_refused(pl)) return rc;
+  for (int i = 0; i < nm; ++i)
+    if (wave_ndeg(pl->L, m_host[i]) > WAVECLS_NDEG_MAX)
+      return fail(TEMX_EUNSUPPORTED, "wavenumber %d at L = %d has %d degrees: the class form serves at most %d; use the generic form",
+                  m_host[i], pl->L, wave_ndeg(pl->L, m_host[i]), WAVECLS_NDEG_MAX);
+  HIPCHK(hipSetDevice(pl->device));
+  HIPCHK(hipDeviceSynchronize());
+  temxz_wave* z = new temxz_wave();
+  temxk_wave* w = &z->g;
+  w->pl = pl;
+  w->device = pl->device;
+  auto bail = [&](int code) {
+    delete z;
+    return code;
+  };
+  const double d2r = M_PI / 180.0;
+  std::vector<double> lat((size_t)pl->N), lon((size_t)pl->N), lat_out((size_t)pl->M);
+  for (int64_t i = 0; i < pl->N; ++i) lat[(size_t)i] = pl->h_lat[(size_t)i] * d2r, lon[(size_t)i] = lon_deg_host[i] * d2r;
+  for (int j = 0; j < pl->M; ++j) lat_out[(size_t)j] = pl->lat_out_deg[(size_t)j] * d2r;
+  int rc, zero = 0;
+  DevBuf rep;                   // one representative row per class and side: build time only
+  struct Free {
+    DevBuf& a;
+    ~Free() { a.release(); }
+  } free_{rep};
+  if ((rc = upload(w->lat, lat)) || (rc = upload(w->lon, lon)) || (rc = upload(w->lat_out, lat_out)) ||
+      (rc = upload(w->flag, &zero, sizeof zero)) ||
+      (rc = upload(rep, wavecls_representatives(pl->h_crow, pl->gbatch0, pl->cgroups))))
+    return bail(rc);
+  w->ms.resize((size_t)nm);
+  z->cm.resize((size_t)nm);
+  for (int i = 0; i < nm; ++i) {
+    w->ms[(size_t)i].m = m_host[i];
+    w->ms[(size_t)i].sh = wave_shape(pl->L, m_host[i]);
+    z->cm[(size_t)i].sh = wavecls_shape(pl->L, m_host[i]);
+    w->kc_max = std::max(w->kc_max, w->ms[(size_t)i].sh.Kc);
+  }
+  for (int i = 0; i < nm; ++i) {
+    WaveClsM& cm = z->cm[(size_t)i];
+    if ((rc = upload(cm.cw, wavecls_weights(pl->h_crow, lon.data(), m_host[i])))) return bail(rc);
+    if ((rc = wave_build_m(w, w->ms[(size_t)i], &cm, static_cast<const int*>(rep.p)))) return bail(rc);
+  }
+  w->partial.release();          // the slabs of the Gram sweeps: sized for the generic sweep
+  *out = z;
+  return TEMX_OK;
+} TEMX_CATCH
+
+void temxz_wave_destroy(temxz_wave* z) {
+  if (!z) return;
+  (void)hipSetDevice(z->g.device);   // (the plan may be gone already)
+  (void)hipDeviceSynchronize();
+  delete z;
+}
+
+int64_t temxz_wave_workspace_bytes(const temxz_wave* z) {
+  if (!z) return 0;
+  size_t n = (size_t)temxk_wave_workspace_bytes(&z->g);
+  for (const WaveClsM& c : z->cm) n += c.tab.bytes + c.cw.bytes;
+  return (int64_t)n;
+}
+
+int temxz_wave_project(temxz_wave* z, int mi, int nf, const void* const* fields_host, const int* dtype_host, int64_t D,
+                       double* parts, double* coef_or_null, void* stream) try {
+  if (!z || !fields_host || !dtype_host || !parts) return fail(TEMX_EINVAL, "null argument");
+  temxk_wave* w = &z->g;
+  if (mi < 0 || mi >= (int)w->ms.size()) return fail(TEMX_EINVAL, "mi must lie in 0..%d, got %d", (int)w->ms.size() - 1, mi);
+  if (nf < 1 || nf > WAVE_NF_MAX) return fail(TEMX_EINVAL, "nf must lie in 1..%d, got %d", WAVE_NF_MAX, nf);
+  for (int f = 0; f < nf; ++f) {
+    if (!fields_host[f]) return fail(TEMX_EINVAL, "field %d is null", f);
+    if (dtype_host[f] != TEMX_F64 && dtype_host[f] != TEMX_F32) return bad_dtype();
+  }
+  if (D < 1 || D >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "D must be in [1, 2^28)");
+  temx_plan* pl = w->pl;
+  if (int rc = wavecls_plan_refused(pl)) return rc;
+  HIPCHK(hipSetDevice(pl->device));
+  hipStream_t st = S_(stream);
+  const WaveM& wm = w->ms[(size_t)mi];
+  const int64_t KD = (int64_t)wm.sh.Kc * D, MD = (int64_t)pl->M * D;
+  int rc;
+  if ((rc = wave_ensure(w, 1, D))) return rc;
+  for (int f = 0; f < nf; ++f) {
+    FieldPtrs<1> fp;
+    fp.p[0] = fields_host[f];
+    double* C = coef_or_null ? coef_or_null + f * KD : w->C.d();
+    if ((rc = wavecls_sweep<1>(z, (size_t)mi, fp, dtype_host[f], D, nullptr, -1, w->B.d(), st))) return rc;
+    if ((rc = wave_solve(wm, 1, D, w->B.d(), C, st))) return rc;
+    hipLaunchKernelGGL(wave_parts_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)pl->M, 1), dim3(256), 0, st,
+                       (const double*)C, wm.sh.ndeg, pl->M, D, (const double*)wm.pz.d(), parts + f * 2 * MD);
+    HIPCHK(hipGetLastError());
+  }
+  return TEMX_OK;
+} TEMX_CATCH
+
+int temxz_wave_fluxes(temxz_wave* z, const void* ua, const void* va, const void* ta, const void* wap, int dtype,
+                      double* flux, double* parts_or_null, void* stream) try {
+  if (!z || !ua || !va || !ta || !wap || !flux) return fail(TEMX_EINVAL, "null argument");
+  if (dtype != TEMX_F64 && dtype != TEMX_F32) return bad_dtype();
+  temxk_wave* w = &z->g;
+  temx_plan* pl = w->pl;
+  if (int rc = tem_ready(pl)) return rc;
+  if (int rc = wavecls_plan_refused(pl)) return rc;
+  HIPCHK(hipSetDevice(pl->device));
+  hipStream_t st = S_(stream);
+  const int64_t D = pl->D, MD = (int64_t)pl->M * D;
+  int rc;
+  if ((rc = wave_ensure(w, 4, D))) return rc;
+  const FieldPtrs<4> fp = four(ua, va, ta, wap);
+  for (size_t i = 0; i < w->ms.size(); ++i) {
+    const WaveM& wm = w->ms[i];
+    // theta = T (p0/p)^kappa: the column scale of field 2, applied to its class sums (the sweep is linear)
+    if ((rc = wavecls_sweep<4>(z, i, fp, dtype, D, pl->colscale.d(), 2, w->B.d(), st))) return rc;
+    if ((rc = wave_solve(wm, 4, D, w->B.d(), w->C.d(), st))) return rc;
+    hipLaunchKernelGGL(wave_flux_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)pl->M), dim3(256), 0, st,
+                       (const double*)w->C.d(), wm.sh.ndeg, pl->M, D, (const double*)wm.pz.d(), flux + (int64_t)i * 3 * MD,
+                       parts_or_null ? parts_or_null + (int64_t)i * 8 * MD : (double*)nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  return TEMX_OK;
+} TEMX_CATCH
+
+int temxz_wave_status(temxz_wave* z, int* nonfinite_host, void* stream) try {
+  if (!z || !nonfinite_host) return fail(TEMX_EINVAL, "null argument");
+  return temxk_wave_status(&z->g, nonfinite_host, stream);
+} TEMX_CATCH
+
+// wavecls_shape of wave_class_tables.hpp (no device, no state)
+int temxz_wave_shape(int L, int m, int* shape_host) try {
+  if (!shape_host) return fail(TEMX_EINVAL, "null argument");
+  if (L < 1 || L > 511 || m < 1 || m > L) return fail(TEMX_EINVAL, "L must lie in 1..511 and m in 1..L, got L = %d, m = %d", L, m);
+  if (wave_ndeg(L, m) > WAVECLS_NDEG_MAX)
+    return fail(TEMX_EUNSUPPORTED, "L = %d, m = %d has %d degrees: the class form serves at most %d", L, m, wave_ndeg(L, m),
+                WAVECLS_NDEG_MAX);
+  const WaveClsShape s = wavecls_shape(L, m);
+  const int v[5] = {s.ndeg, s.Kc, s.TBS, s.nacc, s.fpw};
+  std::copy(v, v + 5, shape_host);
+  return TEMX_OK;
+} TEMX_CATCH
+
+// the cut of a sweep, as wavecls_sweep makes it (host arithmetic only)
+int temxz_wave_launch(const temxz_wave* z, int mi, int nf, int64_t D, int* out_host) try {
+  if (!z || !out_host) return fail(TEMX_EINVAL, "null argument");
+  if (mi < 0 || mi >= (int)z->cm.size()) return fail(TEMX_EINVAL, "mi must lie in 0..%d, got %d", (int)z->cm.size() - 1, mi);
+  if (nf != 1 && nf != 4) return fail(TEMX_EINVAL, "nf must be 1 (the sweep of a projection) or 4 (the sweep of the fluxes), got %d", nf);
+  if (D < 1 || D >= ((int64_t)1 << 28)) return fail(TEMX_EINVAL, "D must be in [1, 2^28)");
+  const temx_plan* pl = z->g.pl;
+  const Split sp = nf == 4 ? wavecls_split<4>(pl, D) : wavecls_split<1>(pl, D);
+  out_host[0] = z->cm[(size_t)mi].sh.TBS;
+  out_host[1] = sp.ndt;
+  out_host[2] = sp.nsplit;
+  out_host[3] = wavecls_cuts_inside(pl->gbatch0, pl->cgroups, pl->cbatches, sp.nsplit);
   return TEMX_OK;
 } TEMX_CATCH
 

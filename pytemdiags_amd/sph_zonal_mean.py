@@ -45,13 +45,16 @@ class sph_zonal_averager:
 
     def __init__(self, lat, lat_out, L, weights=None, grid_name=None, grid_out_name=None,
                  ncoldim="ncol", overwrite=False, save_dest=None, debug=False, logfile=None,
-                 device=None, fp32_fields=False, missing="raise", min_coverage=0.5, *, lat_bins=None, lon=None):
+                 device=None, fp32_fields=False, missing="raise", min_coverage=0.5, *, lat_bins=None, lon=None,
+                 wave_form="generic"):
         self.L = L
-        # (not in the reference's signature) lon=: the longitudes of the native columns in degrees, for sph_wave
+        # (not in the reference's signature) lon=: the longitudes of the native columns in degrees, for sph_wave;
+        # wave_form="classes": sph_wave runs the class form of the fit (waves.py)
+        from . import waves
         self._lon = None
         self._waves = {}
+        self._wave_form = waves.check_form(wave_form, lon is not None, what="lon=")
         if lon is not None:
-            from . import waves
             self._lon = waves.check_lon(lon, len(_as_numpy(lat)))
         # (not in the reference's signature) missing="mask": non-finite values are missing points of a masked fit
         # instead of an error; outputs whose coverage is below min_coverage are NaN (include/temx.h)
@@ -311,7 +314,7 @@ class sph_zonal_averager:
         if t.dtype not in (torch.float64, torch.float32):
             t = t.to(torch.float64)
         if m not in self._waves:
-            self._waves[m] = waves.WaveState(self._plan, self._lon, (m,))
+            self._waves[m] = waves.WaveState(self._plan, self._lon, (m,), form=self._wave_form)
         parts = self._waves[m].project(t.to(self._plan.device), m)
         if self._waves[m].status():
             raise RuntimeError("Variable {} has nans! Spectral zonal averager cannot handle nans; "

@@ -45,12 +45,14 @@ class TEMDiagnostics:
                  overwrite_map=False, zm_pole_points=False, debug_level=1, logfile=None,
                  *, plev=None, time=None, dims=None, device=None, missing="raise", min_coverage=0.5, time_block=None,
                  lat_bins=None, climatology=False, tracer_mask=None, min_time_coverage=None, time_groups=None,
-                 time_weights=None, min_group_coverage=None, lon=None, wavenumbers=None, time_bands=None):
+                 time_weights=None, min_group_coverage=None, lon=None, wavenumbers=None, time_bands=None,
+                 wave_form="generic"):
         # ---- zonal wavenumbers (not in the reference; waves.py): checked before anything touches the device ----
         self._waves, self._wave_args = None, None
+        self._wave_form = wv.check_form(wave_form, wavenumbers is not None)
         if wavenumbers is not None:
             self._wave_args = wv.check_arguments(wavenumbers, lon, len(lat_native), L, missing=missing, lat_bins=lat_bins,
-                                                 time_block=time_block, climatology=climatology)
+                                                 time_block=time_block, climatology=climatology, wave_form=wave_form)
         # ---- EP flux by time scale (not in the reference; timebands.py): checked before anything touches the device ----
         # (the record's length is checked in _config_dims, still before the device)
         self._bands, self._band_args = None, None
@@ -149,7 +151,8 @@ class TEMDiagnostics:
             self._bands = self._band_builder.finish(self._zon)
             self._band_builder = None
         if self._wave_args is not None:     # the plan is still set for the ordinary run, whose zonal means the sets share
-            self._waves = wv.build(self, plan, self._wave_args[1], self._wave_args[0], self._dev_fields, self._zon)
+            self._waves = wv.build(self, plan, self._wave_args[1], self._wave_args[0], self._dev_fields, self._zon,
+                                   form=self._wave_form)
 
     @property
     def waves(self):
@@ -364,10 +367,11 @@ class TEMDiagnostics:
             raise ValueError("missing must be 'raise' or 'mask', got %r" % (kw["missing"],))
         cls._check_tracer_mask(kw.get("tracer_mask"), kw.get("missing", "raise"), q)
         cls._check_lat_bins(kw.get("lat_bins"), kw.get("missing", "raise"))
+        wv.check_form(kw.get("wave_form", "generic"), kw.get("wavenumbers") is not None)
         if kw.get("wavenumbers") is not None:
             wv.check_arguments(kw["wavenumbers"], kw.get("lon"), len(lat_native), kw.get("L", 50), missing=kw.get("missing", "raise"),
                                lat_bins=kw.get("lat_bins"), time_block=kw.get("time_block"),
-                               climatology=kw.get("climatology", False))
+                               climatology=kw.get("climatology", False), wave_form=kw.get("wave_form", "generic"))
         if kw.get("time_bands") is not None:
             tb.check_record(tb.check_arguments(kw["time_bands"], missing=kw.get("missing", "raise"), time_block=kw.get("time_block"),
                                                climatology=kw.get("climatology", False), wavenumbers=kw.get("wavenumbers")),

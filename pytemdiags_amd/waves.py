@@ -18,6 +18,12 @@ up to the ordinary run's (``epdiv`` consumes the already-cast ``epfy`` / ``epfz`
 The sum over m alone is NOT the total: noise, and the leakage between m and m +- 4 on a cubed sphere, stay in the
 residual.  The numbers come from the HIP engine (pytemdiags_amd/include/temx_wave.h); this module
 validates, drives and labels.
+
+``wave_form="classes"`` (default ``"generic"``) runs the same fit in its class form (pytemdiags_amd/include_wavecls/temx_wavecls.h,
+DESIGN.md 8c): on a grid whose columns share latitudes -- a cubed sphere, a lat-lon or Gaussian grid -- the sums of the fit
+are formed per latitude class and the state keeps a few bytes per column instead of a basis of ``2 (L + 1 - m)`` columns.
+It serves ``L + 1 - m <= 64``; a grid without latitude classes and a wider basis are refused with a ``ValueError`` that
+names the generic form.  Nothing selects it automatically.
 """
 from __future__ import annotations
 
@@ -29,6 +35,7 @@ from . import _lib
 from . import climatology as clim
 
 FIELD_NAMES = ("ua", "va", "theta", "wap")
+WAVE_FORMS = ("generic", "classes")
 _FIELD_SRC = {"ua": "ua", "va": "va", "theta": "ta", "wap": "wap"}
 
 
@@ -67,8 +74,20 @@ def check_lon(lon, ncol):
     return v
 
 
-def check_arguments(wavenumbers, lon, ncol, L, *, missing="raise", lat_bins=None, time_block=None, climatology=False):
+def check_form(wave_form, have_wavenumbers=True, what="wavenumbers="):
+    """``wave_form`` as one of ``WAVE_FORMS`` (ValueError otherwise, and for the class form without ``what``).  Host
+    logic only."""
+    if not isinstance(wave_form, str) or wave_form not in WAVE_FORMS:
+        raise ValueError("wave_form must be one of %s, got %r" % (WAVE_FORMS, wave_form))
+    if wave_form == "classes" and not have_wavenumbers:
+        raise ValueError("wave_form='classes' needs %s: it is a form of the wave fit" % what)
+    return wave_form
+
+
+def check_arguments(wavenumbers, lon, ncol, L, *, missing="raise", lat_bins=None, time_block=None, climatology=False,
+                    wave_form="generic"):
     """Everything ``TEMDiagnostics`` refuses next to ``wavenumbers=`` before any device work -> (tuple of m, lon)."""
+    check_form(wave_form)
     ms = check_wavenumbers(wavenumbers, L)
     lon = check_lon(lon, ncol)
     for on, what, why in ((missing == "mask", "missing='mask'", "a masked wave fit"),
@@ -81,26 +100,51 @@ def check_arguments(wavenumbers, lon, ncol, L, *, missing="raise", lat_bins=None
 
 
 class WaveState:
-    """The engine's wave state (temxk_wave) of some wavenumbers on a finalised plan.  It uses the plan: close it first."""
+    """The engine's wave state of some wavenumbers on a finalised plan: the generic form (temxk_wave) or, with
+    ``form="classes"``, the class form (temxz_wave), which has the same calls.  It uses the plan: close it first."""
 
-    def __init__(self, plan, lon_deg, wavenumbers):
-        from . import _wave
-        self.lib = _wave.load()
+    def __init__(self, plan, lon_deg, wavenumbers, form="generic"):
+        self.form = check_form(form)
+        if self.form == "classes":
+            from . import _wavecls
+            self.lib, self._prefix = _wavecls.load(), "temxz_wave_"
+        else:
+            from . import _wave
+            self.lib, self._prefix = _wave.load(), "temxk_wave_"
         self.plan = plan
         self.wavenumbers = tuple(int(m) for m in wavenumbers)
         self._h = C.c_void_p()
         lon = np.ascontiguousarray(lon_deg, dtype=np.float64)
         ms = (C.c_int * len(self.wavenumbers))(*self.wavenumbers)
-        _lib.check(self.lib.temxk_wave_create(C.byref(self._h), plan._h, lon.ctypes.data_as(C.POINTER(C.c_double)),
-                                              len(self.wavenumbers), ms))
+        try:
+            _lib.check(self._fn("create")(C.byref(self._h), plan._h, lon.ctypes.data_as(C.POINTER(C.c_double)),
+                                          len(self.wavenumbers), ms))
+        except _lib.TemxError as e:
+            # what only the class form refuses (a grid without latitude classes, more than 64 degrees) is a choice of
+            # the caller's, not a failure of the engine: the way out is the generic form
+            if self.form == "classes" and e.code == -6 and "generic form" in str(e):
+                raise ValueError("wave_form='classes' does not serve this case: %s" % e) from None
+            raise
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
 
     @property
     def workspace_bytes(self):
-        return int(self.lib.temxk_wave_workspace_bytes(self._h)) if self._h.value else 0
+        return int(self._fn("workspace_bytes")(self._h)) if self._h.value else 0
+
+    def launch(self, m, nf, D):
+        """Class form only: how the sweep of ``nf`` (4: the fluxes, 1: a projection) fields of ``D`` columns is cut, as
+        ``_wavecls.launch`` gives it."""
+        from . import _wavecls
+        if self.form != "classes":
+            raise ValueError("launch describes the class form: build the state with form='classes'")
+        self._live()
+        return _wavecls.launch(self._h, self.wavenumbers.index(int(m)), nf, D)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.temxk_wave_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -113,7 +157,7 @@ class WaveState:
         """Synchronise; True when a non-finite value reached the sums of ``project`` / ``fluxes`` since the last call."""
         self._live()
         f = C.c_int(0)
-        _lib.check(self.lib.temxk_wave_status(self._h, C.byref(f), self.plan._stream()))
+        _lib.check(self._fn("status")(self._h, C.byref(f), self.plan._stream()))
         return bool(f.value)
 
     def _live(self):
@@ -135,8 +179,8 @@ class WaveState:
             coef = torch.empty((2 * (plan.L + 1 - int(m)), D), dtype=torch.float64, device=plan.device)
         fields = (C.c_void_p * 1)(A.data_ptr())
         dts = (C.c_int * 1)(_DT[A.dtype])
-        _lib.check(self.lib.temxk_wave_project(self._h, self.wavenumbers.index(int(m)), 1, fields, dts, D, _ptr(parts),
-                                               _ptr(coef) if coef is not None else None, plan._stream()))
+        _lib.check(self._fn("project")(self._h, self.wavenumbers.index(int(m)), 1, fields, dts, D, _ptr(parts),
+                                        _ptr(coef) if coef is not None else None, plan._stream()))
         return (parts, coef) if want_coef else parts
 
     def fluxes(self, ua, va, ta, wap, want_parts=False):
@@ -152,8 +196,8 @@ class WaveState:
         parts = None
         if want_parts:
             parts = torch.empty((nm, 4, 2, plan.M, plan.nlev, plan.nt), dtype=torch.float64, device=plan.device)
-        _lib.check(self.lib.temxk_wave_fluxes(self._h, _ptr(u), _ptr(v), _ptr(t), _ptr(w), dt, _ptr(flux),
-                                              _ptr(parts) if parts is not None else None, plan._stream()))
+        _lib.check(self._fn("fluxes")(self._h, _ptr(u), _ptr(v), _ptr(t), _ptr(w), dt, _ptr(flux),
+                                       _ptr(parts) if parts is not None else None, plan._stream()))
         return flux, parts
 
 
@@ -197,10 +241,11 @@ class TEMWaves:
     """``tem.waves``: ``wavenumbers``, ``tem.waves[m]``, ``residual``, ``workspace_bytes`` (device bytes the engine's
     wave state held: the stored bases, ncol x Kc x 8 bytes per wavenumber, and the workspace of the run)."""
 
-    def __init__(self, wavenumbers, sets, residual, workspace_bytes):
+    def __init__(self, wavenumbers, sets, residual, workspace_bytes, form="generic"):
         self.wavenumbers = tuple(wavenumbers)
         self.residual = residual
         self.workspace_bytes = int(workspace_bytes)
+        self.form = form                          # "generic" or "classes": the form of the fit that made the sets
         self._sets = dict(zip(self.wavenumbers, sets))
 
     def __getitem__(self, m):
@@ -216,10 +261,10 @@ class TEMWaves:
         return len(self.wavenumbers)
 
 
-def build(owner, plan, lon, wavenumbers, fields, zon):
+def build(owner, plan, lon, wavenumbers, fields, zon, form="generic"):
     """The wave sets of a finished ordinary run: ``plan`` still set for its (nlev, nt), ``fields`` the four device
     fields, ``zon`` its sixteen zonal intermediates (whose seven zonal means the sets share).  -> TEMWaves."""
-    state = WaveState(plan, lon, wavenumbers)
+    state = WaveState(plan, lon, wavenumbers, form=form)
     try:
         flux, parts = state.fluxes(*fields, want_parts=True)      # (the ordinary run has refused non-finite fields)
         nbytes = state.workspace_bytes
@@ -234,4 +279,4 @@ def build(owner, plan, lon, wavenumbers, fields, zon):
         sets.append(WaveSet(owner, "wave%d" % m, res, z, m=m, parts=parts[i]))
     zm7[i0:i0 + 3] = zon[i0:i0 + 3] - flux.sum(dim=0)
     res, z = plan.tem_from_zonal_means(zm7, want_zonal=True)
-    return TEMWaves(wavenumbers, sets, WaveSet(owner, "residual", res, z), nbytes)
+    return TEMWaves(wavenumbers, sets, WaveSet(owner, "residual", res, z), nbytes, form)
